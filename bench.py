@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the DHD-S view-transform hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input resident in HBM:
     MGHS : height argmax -> band, context re-layout, geometry + grouping (prepare),
@@ -11,7 +11,12 @@ at the DHD-S shapes of projects/configs/DHD/DHD-S.py (6 cameras 256x704 -> 16x44
 D=44, C=64, grids 200x200x{1,4,4,8}, samples_per_gpu=4).  Samples are independent, so ranks
 shard them with no data-path collective ("weak" scaling); rank 0 prints ONE JSON line.
 
-The line also carries
+A plain run sets up, runs W warm-up steps, times ONE loop of exactly K steps (`ms_per_step` = its wall time / K,
+`value` = samples/s) and prints the line; `--dump-outputs DIR` writes what the last timed step returned (rank 0) as
+DIR/<name>.npy.  Everything else the benchmark measures runs with `--full` only: R repeats of the loop (`--repeats`,
+default 7 there) with HIP events around the parts, fresh-process repeats, the bf16x6 step, and the records below.
+
+With --full the line also carries
   roofline            : achieved HBM GB/s of the dominant kernel (mghs_stream_fwd), algorithmic bytes
                          / mean launch duration from HIP events on the launch stream
   roofline_bwd        : the same for the pooling backward (mghs_stream_bwd + mghs_pixel_bwd, 177.7 MB/sample)
@@ -199,12 +204,21 @@ def parse():
     p.add_argument('--no-ddp-static-graph', dest='ddp_static_graph', action='store_false',
                    help='e2e under DDP: DistributedDataParallel(static_graph=False) (default: static_graph=True -- the step has the same '
                         'autograd graph every iteration; exercised with two ranks over gloo incl. the no_sync() comparison)')
-    p.add_argument('--repeats', type=int, default=7,
+    p.add_argument('--repeats', type=int, default=None,
                    help='hotpath: the timed loop of EXACTLY --steps steps is run this many times in the process (barrier + synchronize on both '
-                        'sides each time); ms_per_step / value are the median loop, min / max / all are reported beside it')
+                        'sides each time); ms_per_step / value are the median loop, min / max / all are reported beside it (default: 1, '
+                        'with --full 7)')
     p.add_argument('--fresh-procs', type=int, default=2,
-                   help='hotpath, N = 1: repeat the whole measurement in this many fresh processes (other allocator placement of the 0.7 GB '
-                        'outputs: one build differs by up to 11 % on the writer between two processes on one box)')
+                   help='hotpath, N = 1, --full: repeat the whole measurement in this many fresh processes (other allocator placement of the '
+                        '0.7 GB outputs: one build differs by up to 11 %% on the writer between two processes on one box)')
+    p.add_argument('--full', action='store_true',
+                   help='hotpath: everything beyond the headline -- HIP-event parts and rooflines, the bf16x6 step, HBM calibration, lift '
+                        'timing, the DHD-L and fresh-process children, the half-precision and operator records, the CPU baseline and the '
+                        'e2e sub-record.  Without it the run times the --steps steps once and prints the headline line only')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='hotpath: after the timed steps, write what the last one returned (rank 0: pooled grids, depth / context '
+                        'gradients, SFA stage output and gradients; a fixed seeded sample of each array above 2^20 elements) as '
+                        'DIR/<name>.npy, float32')
     p.add_argument('--no-dhdl', action='store_true', help='hotpath: leave out the MGHS-only record at the DHD-L geometry (configs[3]/[4], B = 2)')
     p.add_argument('--pmc-pass', action='store_true',
                    help='hotpath: only what a counter-collection pass needs -- one timed loop, the bf16x6 loop and the three-step operator; no '
@@ -222,8 +236,14 @@ def parse():
                    help='(test only) --workload e2e on a few-kilobyte stand-in detector that runs on CPU tensors: exercises the launcher, the '
                         'process group, DDP and the record plumbing without a GPU (tests/test_distributed.py); the line is marked "stub"')
     a = p.parse_args()
+    if a.pmc_pass or a.child:   # both are forms of the extended measurement (a counter pass, a fresh-process repeat)
+        a.full = True
     if a.pmc_pass:
         a.no_dhdl, a.fresh_procs, a.repeats, a.no_e2e, a.cpu_samples = True, 0, 1, True, 0
+    if a.repeats is None:
+        a.repeats = 7 if a.full else 1
+    if a.dump_outputs and a.workload != 'hotpath':
+        p.error('--dump-outputs writes the hot path\'s outputs (--workload hotpath)')
     return a
 
 
@@ -322,7 +342,20 @@ class HotPath:
             else:
                 y = self.stage(self.x)
                 y.backward(self.gy)
-        return outs, dg, fg_nchw
+        else:
+            y = None
+        return outs, dg, fg_nchw, y
+
+    def outputs(self, last):
+        """What a caller of the step receives from its call `last` (= step's return value), as name -> tensor: the pooled grids,
+        the depth and context gradients; with the SFA stage its output, the input gradient and the parameter gradients."""
+        outs, dg, fg, y = last
+        d = {f'mghs_out{k}': o for k, o in enumerate(outs)}
+        d.update(mghs_depth_grad=dg, mghs_feat_grad=fg)
+        if y is not None:
+            d.update(sfa_out=y.detach(), sfa_x_grad=self.x.grad)
+            d.update({f'sfa_grad.{n}': p.grad for n, p in self.stage.named_parameters() if p.grad is not None})
+        return d
 
 
 class _StubDetector(torch.nn.Module):
@@ -482,6 +515,27 @@ class EndToEnd:
         if self.ema is not None:
             self.ema.update(None, self.model)
         return loss
+
+
+DUMP_SAMPLE = 1 << 20   # --dump-outputs: larger arrays are written as this many elements at fixed, seeded positions
+
+
+def dump_outputs(arrays, out_dir, seed=0):
+    """Write name -> tensor as out_dir/<name>.npy in float32 (float64 stays float64).  An array of more than DUMP_SAMPLE elements
+    is written as DUMP_SAMPLE of its elements (flattened, row-major) at sorted positions drawn from a generator seeded by `seed`
+    and the array's size: the same positions in every run with the same arguments.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            pos = np.random.default_rng([seed, t.numel()]).choice(t.numel(), DUMP_SAMPLE, replace=False)
+            t = t.index_select(0, torch.from_numpy(np.sort(pos)).to(t.device))
+        v = t.cpu().numpy()
+        v = v if v.dtype == np.float64 else v.astype(np.float32)
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+        total += v.nbytes
+    return total
 
 
 def fence():
@@ -1378,12 +1432,19 @@ def main():
         have = torch.cuda.device_count()
         if have < a.gpus and a.dist_backend != 'gloo':   # gloo (test only): ranks may share a GPU (or have none: --stub-model)
             raise SystemExit(f'--gpus {a.gpus} requested but only {have} GPU(s) are visible')
+        import signal
         import socket
+        import subprocess
         with socket.socket() as sock:
             sock.bind(('127.0.0.1', 0))
             port = sock.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={a.gpus}',
-                                  '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        # a child process, not exec: this process has initialised the HIP runtime above
+        proc = subprocess.Popen([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={a.gpus}',
+                                 '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        for sig in (signal.SIGTERM, signal.SIGINT):
+            signal.signal(sig, lambda s, _: proc.send_signal(s))
+        rc = proc.wait()
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     rank, local, world = ddist.env_world()
     if world != a.gpus:
         raise SystemExit(f'--gpus {a.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {a.gpus} (or without a launcher)')
@@ -1408,17 +1469,20 @@ def main():
     for _ in range(a.warmup):
         hp.step(False)
 
-    # R repeats of the timed loop of exactly K steps; each repeat has its own fences and its own event samples
-    def timed_loop(record=True):
+    # R repeats of the timed loop of exactly K steps; each repeat has its own fences and its own event samples (--full)
+    def timed_loop(record=True, keep=False):
         hp.ev, hp.ev_bwd, hp.ev_sfa = [], [], []
-        hp.make_events((a.steps + 3) // 4)
+        if record:
+            hp.make_events((a.steps + 3) // 4)
+        kept['last'] = last = None   # an earlier loop's results are not held while this one runs
         with no_gc():   # a cyclic collection inside the timed steps is a 30-40 ms host pause in a 0.1 s region
             fence()
             t0 = time.perf_counter()
             for k in range(a.steps):
                 # HIP events around the dominant kernel / the backward / the SFA stage on every 4th timed step (and the first): each
                 # recorded step carries seven extra marker packets and host calls, 35 us on a 0.34 ms MGHS-only step
-                hp.step(record and k % 4 == 0)
+                last = None   # the previous step's results go back to the allocator before this step, as if never kept
+                last = hp.step(record and k % 4 == 0)
             fence()
             mine = time.perf_counter() - t0
             el = ddist.max_over_ranks(mine, dev)
@@ -1427,10 +1491,19 @@ def main():
         if record and hp.ev_sfa:
             parts['sfa_fwd_ms'] = event_mean([(e[0], e[1]) for e in hp.ev_sfa])
             parts['sfa_bwd_ms'] = event_mean([(e[1], e[2]) for e in hp.ev_sfa])
+        if keep:
+            kept['last'] = last
         return el, parts
 
     own_ms = []   # this rank's own loop times (the headline is the MAX over ranks per loop)
-    reps = [timed_loop() for _ in range(max(1, a.repeats))]
+    kept = {}     # the return value of the last step of the latest loop
+    reps = [timed_loop(record=a.full, keep=bool(a.dump_outputs)) for _ in range(max(1, a.repeats))]
+    if a.dump_outputs and rank == 0 and kept['last'] is not None:
+        t_stage = time.perf_counter()
+        nbytes = dump_outputs(hp.outputs(kept['last']), a.dump_outputs)
+        print(f'[bench] outputs of the last timed step: {nbytes / 2**20:.1f} MiB in {a.dump_outputs} '
+              f'({time.perf_counter() - t_stage:.1f} s)', file=sys.stderr, flush=True)
+    kept.clear()
     # every rank describes itself (backend, world size as the process group reports it, device, own step time): identical on all ranks
     dist_report = ddist.rank_report(ms_per_step_own=float(np.median(own_ms)))
     per_step = sorted(1e3 * el / a.steps for el, _ in reps)
@@ -1445,6 +1518,32 @@ def main():
         ddist.shutdown()
         return
 
+    line = None
+    if rank == 0:
+        line = dict(
+            metric=f'samples/sec (6-cam fwd+bwd) {a.geometry.upper()} view-transform hot path', value=a.batch * world * a.steps / elapsed,
+            unit='samples/s', n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=1e3 * elapsed / a.steps,
+            higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f32', data='synthetic',
+            config=dict(workload=('DHD-S (configs[1])' if a.geometry == 'dhd-s' else a.geometry.upper() + ' geometry (configs[3-4])') + ' hot path: MGHS 4-grid lift-splat fwd+bwd incl. geometry/grouping'
+                                 + ('' if a.no_sfa else ' + SFA attention stage fwd+bwd') +
+                                 f'; geometry {a.geometry}: 6 cams -> {hp.dims[2]}x{hp.dims[3]}, D={hp.dims[1]}, C=64, grids 200x200x{{1,4,4,8}}; dense backbone/encoder convs not in the step',
+                        samples_per_gpu=a.batch, global_batch=a.batch * world, parallelism=f'sample-sharded x{world}, no data-path collective' +
+                        ('' if world == 1 else ': `value` is the collective-free hot path (N independent replicas of the per-GPU work); the DDP / RCCL '
+                         'step north_star asks for at this N is the top-level `e2e_scaling` record (--full)'),
+                        deterministic_forward=bool(a.deterministic),
+                        sfa_gemm=None if a.no_sfa else (a.sfa_gemm or 'bf16x3') +
+                        ' (float32 operands cut into bf16 parts for the bf16 MFMA, float32 accumulate; bf16x3 = 2 parts / 3 products per a*b, '
+                        'stage output within 2.2e-5 of float64; bf16x6 = 3 parts / 6 products, float32-level; storage, element-wise '
+                        'arithmetic and statistics are float32 in both)'))
+    if not a.full:   # the headline only: the rest of the record is --full
+        if rank == 0:
+            line['distributed'] = dist_report
+            line['miopen_db'] = MIOPEN_DB
+            line.update(repeats=len(reps), ms_per_step_min=per_step[0], ms_per_step_max=per_step[-1])
+            print(json.dumps(line), flush=True)
+        leave()
+        return
+
     # the same step with float32-level GEMM products in the SFA stage (bf16x6), W warm-ups + K timed steps
     elapsed_x6 = None
     if hp.with_sfa and (a.sfa_gemm or 'bf16x3') != 'bf16x6':
@@ -1456,25 +1555,10 @@ def main():
     cal_ms, cal_bytes = hbm_calibration(dev, hp.pool_fwd_bytes)   # every rank runs it, rank 0 reports
     lift_us = lift_timing(hp)
 
-    line = None
     if rank == 0:
         kern_ms = part_stats['writer_ms']['median']
         achieved = hp.pool_fwd_bytes / (kern_ms * 1e-3) / 1e9
-        line = dict(
-            metric=f'samples/sec (6-cam fwd+bwd) {a.geometry.upper()} view-transform hot path', value=a.batch * world * a.steps / elapsed,
-            unit='samples/s', n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=1e3 * elapsed / a.steps,
-            higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f32', data='synthetic',
-            config=dict(workload=('DHD-S (configs[1])' if a.geometry == 'dhd-s' else a.geometry.upper() + ' geometry (configs[3-4])') + ' hot path: MGHS 4-grid lift-splat fwd+bwd incl. geometry/grouping'
-                                 + ('' if a.no_sfa else ' + SFA attention stage fwd+bwd') +
-                                 f'; geometry {a.geometry}: 6 cams -> {hp.dims[2]}x{hp.dims[3]}, D={hp.dims[1]}, C=64, grids 200x200x{{1,4,4,8}}; dense backbone/encoder convs not in the step',
-                        samples_per_gpu=a.batch, global_batch=a.batch * world, parallelism=f'sample-sharded x{world}, no data-path collective' +
-                        ('' if world == 1 else ': `value` is the collective-free hot path (N independent replicas of the per-GPU work); the DDP / RCCL '
-                         'step north_star asks for at this N is the top-level `e2e_scaling` record'),
-                        deterministic_forward=bool(a.deterministic),
-                        sfa_gemm=None if a.no_sfa else (a.sfa_gemm or 'bf16x3') +
-                        ' (float32 operands cut into bf16 parts for the bf16 MFMA, float32 accumulate; bf16x3 = 2 parts / 3 products per a*b, '
-                        'stage output within 2.2e-5 of float64; bf16x6 = 3 parts / 6 products, float32-level; storage, element-wise '
-                        'arithmetic and statistics are float32 in both)'),
+        line.update(
             roofline=dict(bound='hbm', kernel='mghs_stream_fwd', achieved=achieved, peak=HBM_PEAK_GBPS, unit='GB/s',
                           frac=achieved / HBM_PEAK_GBPS, traffic=pmc_traffic('mghs_stream_fwd', a.batch), launch_ms=kern_ms,
                           algorithmic_bytes=hp.pool_fwd_bytes,
@@ -1590,8 +1674,8 @@ def fresh_process_repeats(a, n=None, geometry=None, batch=None, no_sfa=None):
     out = []
     no_sfa = a.no_sfa if no_sfa is None else no_sfa
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(a.steps), '--warmup', str(a.warmup), '--repeats', str(a.repeats),
-           '--batch', str(batch or a.batch), '--geometry', geometry or a.geometry, '--child', '--fresh-procs', '0', '--cpu-samples', '0', '--no-e2e',
-           '--no-operator']
+           '--batch', str(batch or a.batch), '--geometry', geometry or a.geometry, '--child', '--full', '--fresh-procs', '0', '--cpu-samples', '0',
+           '--no-e2e', '--no-operator']
     cmd += (['--no-sfa'] if no_sfa else []) + (['--deterministic'] if a.deterministic else []) + (['--sfa-gemm', a.sfa_gemm] if a.sfa_gemm else [])
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     for _ in range(a.fresh_procs if n is None else n):

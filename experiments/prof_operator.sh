@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_operator
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/op -o op -- python $R/bench.py --steps 10 --warmup 3 --cpu-samples 0 --no-e2e --no-sfa 2>/dev/null | grep '^{' > $OUT/bench_op.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/op -o op -- python $R/bench.py --full --steps 10 --warmup 3 --cpu-samples 0 --no-e2e --no-sfa 2>/dev/null | grep '^{' > $OUT/bench_op.json
 cp $(find $OUT/op -name 'op_kernel_stats.csv') $OUT/operator_kernel_stats.csv
 rm -rf $OUT/op
 python - <<'PY'

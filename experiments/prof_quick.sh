@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_quick
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/hp -o hp -- python $R/bench.py --steps 20 --warmup 3 --cpu-samples 0 --no-e2e --no-operator 2>/dev/null | grep '^{' > $OUT/bench_hp.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/hp -o hp -- python $R/bench.py --full --steps 20 --warmup 3 --cpu-samples 0 --no-e2e --no-operator 2>/dev/null | grep '^{' > $OUT/bench_hp.json
 cp $(find $OUT/hp -name 'hp_kernel_stats.csv') $OUT/hotpath_kernel_stats.csv
 rm -rf $OUT/hp
 python - <<'PY'

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/two_ranks
 rm -rf $OUT && mkdir -p $OUT
 cd $R
-common="--gpus 2 --dist-backend gloo --steps 3 --warmup 1 --batch 1 --cpu-samples 0 --no-operator --no-dhdl --fresh-procs 0 --repeats 1"
+common="--full --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --batch 1 --cpu-samples 0 --no-operator --no-dhdl --fresh-procs 0 --repeats 1"
 python bench.py $common --bucket-mb 64 2>$OUT/eager_b64.err | grep '^{' > $OUT/eager_bucket64.json
 python bench.py $common --bucket-mb 64 --ddp-graph 2>$OUT/graph_b64.err | grep '^{' > $OUT/ddp_graph_bucket64.json
 python bench.py $common --bucket-mb 25 2>$OUT/eager_b25.err | grep '^{' > $OUT/eager_bucket25.json

@@ -14,7 +14,7 @@ WHAT="${*:-hotpath ema}"
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [[ " $WHAT " == *" hotpath "* ]]; then
-B="python $R/bench.py --steps 20 --warmup 3 --cpu-samples 0 --no-e2e"
+B="python $R/bench.py --full --steps 20 --warmup 3 --cpu-samples 0 --no-e2e"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/hp -o hp -- $B 2>/dev/null | grep '^{' > $OUT/bench_hotpath_under_rocprof.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/mo -o mo -- $B --no-sfa 2>/dev/null | grep '^{' > $OUT/bench_mghs_only_under_rocprof.json
 P="python $R/bench.py --steps 5 --warmup 2 --pmc-pass"
@@ -114,8 +114,8 @@ PY
 # the plain bench line last, with the fresh PMC summary in place (bench.py reports `traffic` only for a matching source hash)
 if [[ " $WHAT " == *" hotpath "* ]]; then
 mkdir -p $R/profiles/$ROUND && cp $OUT/pmc_summary.json $R/profiles/$ROUND/pmc_summary.json
-cd $R && python bench.py > $OUT/bench_default.json 2>$OUT/bench_default.err
+cd $R && python bench.py --full > $OUT/bench_default.json 2>$OUT/bench_default.err
 # the N > 1 code path on the one-GPU box: two ranks sharing the GPU over gloo (bench.py spawns its own ranks)
-python bench.py --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --batch 1 --cpu-samples 0 --no-operator --no-e2e --no-dhdl 2>$OUT/bench_two_ranks.err | grep '^{' > $OUT/bench_two_ranks_one_gpu_gloo.json
+python bench.py --full --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --batch 1 --cpu-samples 0 --no-operator --no-e2e --no-dhdl 2>$OUT/bench_two_ranks.err | grep '^{' > $OUT/bench_two_ranks_one_gpu_gloo.json
 fi
 ls -la $OUT

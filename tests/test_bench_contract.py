@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields(gpu):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--full',
                           '--no-e2e', '--cpu-samples', '1', '--repeats', '3', '--fresh-procs', '1'], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -45,6 +46,86 @@ def test_bench_prints_one_json_line_with_the_contract_fields(gpu):
     c = d['cpu_baseline']
     assert c['kind'] == 'port' and c['unit'] == 'samples/s' and c['cores'] >= 1 and c['value'] > 0 and 'sample' in c
     assert d['value'] > 50 * c['value']            # sanity: the GPU path is not the CPU twin
+
+
+HEADLINE = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
+            'data', 'config')
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_given_steps_once_and_dumps_the_last_step(gpu, tmp_path):
+    """A plain run (no --full): W warm-ups, ONE loop of exactly K steps, the headline line and nothing else; --dump-outputs
+    writes the last timed step's results as float .npy files (at most 64 MB), the same arrays from run to run."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        t0 = time.perf_counter()
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2',
+                              '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        wall = time.perf_counter() - t0
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in HEADLINE:
+            assert key in line, key
+        assert line['steps'] == 5 and line['warmup'] == 2 and line['repeats'] == 1 and line['dtype'] == 'f32'
+        assert line['unit'] == 'samples/s' and line['higher_is_better'] is True
+        assert abs(line['value'] - 4 * 5 / (line['ms_per_step'] * 5e-3)) < 1e-6 * line['value']
+        assert 0 < line['ms_per_step'] * 5e-3 < wall
+        for key in ('roofline', 'cpu_baseline', 'e2e', 'fresh_processes', 'hotpath_amp', 'roofline_operator', 'roofline_dhdl', 'parts'):
+            assert key not in line, key
+        files = sorted(f.name for f in d.iterdir())
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(f.endswith('.npy') for f in files)
+        assert {'mghs_out0', 'mghs_out3', 'mghs_depth_grad', 'mghs_feat_grad', 'sfa_out', 'sfa_x_grad'} <= set(arrays)
+        assert all(v.dtype in (np.float32, np.float64) and v.size > 0 and np.isfinite(v).all() for v in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 2**20
+        runs.append(arrays)
+    a, b = runs
+    assert set(a) == set(b)
+    for name in a:
+        assert a[name].shape == b[name].shape, name
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-4, atol=1e-5 * max(1.0, float(np.abs(b[name]).max())), err_msg=name)
+
+
+def test_plain_and_full_run_arguments():
+    """--repeats defaults to one loop in a plain run and to seven with --full; a counter pass and a fresh-process child are
+    forms of the full measurement; --dump-outputs belongs to the hot path."""
+    sys.path.insert(0, ROOT)
+    import bench
+    argv = sys.argv
+    try:
+        for args, full, repeats in (([], False, 1), (['--full'], True, 7), (['--repeats', '3'], False, 3),
+                                    (['--pmc-pass'], True, 1), (['--child', '--repeats', '2'], True, 2)):
+            sys.argv = ['bench.py', '--steps', '4'] + args
+            a = bench.parse()
+            assert (a.full, a.repeats, a.steps) == (full, repeats, 4), args
+        sys.argv = ['bench.py', '--workload', 'e2e', '--dump-outputs', 'x']
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_large_arrays(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    n = bench.DUMP_SAMPLE + 12345
+    x = torch.arange(n, dtype=torch.float64) * 0.5
+    arrays = dict(big=x, small=torch.arange(7, dtype=torch.float16), grad=torch.ones(3, 2))
+    nbytes = bench.dump_outputs(arrays, str(tmp_path / 'a'))
+    bench.dump_outputs(arrays, str(tmp_path / 'b'))
+    big = np.load(tmp_path / 'a' / 'big.npy')
+    assert big.dtype == np.float64 and big.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(big) > 0) and big[-1] <= 0.5 * (n - 1)
+    assert np.array_equal(big, np.load(tmp_path / 'b' / 'big.npy'))          # the same positions every run
+    small = np.load(tmp_path / 'a' / 'small.npy')
+    assert small.dtype == np.float32 and np.array_equal(small, np.arange(7, dtype=np.float32))
+    assert np.load(tmp_path / 'a' / 'grad.npy').shape == (6,)
+    assert nbytes == 8 * bench.DUMP_SAMPLE + 4 * 7 + 4 * 6
 
 
 @pytest.mark.gpu

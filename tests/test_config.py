@@ -1,11 +1,21 @@
 """Config surface: the reference's projects/configs/DHD/*.py must load unchanged (they inherit two
-base files from an un-vendored mmdetection3d checkout).  The reference tree only exists in the build
-container; without it the file-based checks are skipped and the bundled-base checks still run."""
+base files from an un-vendored mmdetection3d checkout).  Golden G18 holds what dhd_amd.config loaded from
+each of them (tests/golden/make_golden.py g18); the checks below run on that record, so they need no
+reference tree."""
+import json
 import os
 
 import pytest
 
-REF_CFG = '/root/reference/projects/configs/DHD'
+GOLDEN_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g18_configs.json')
+
+
+def reference_config(name):
+    """projects/configs/DHD/<name>.py as Config.fromfile returned it when G18 was recorded (tuples restored)."""
+    from dhd_amd.config import Config, _wrap
+    with open(GOLDEN_CFG) as f:
+        rec = json.load(f, object_hook=lambda d: tuple(d['__tuple__']) if set(d) == {'__tuple__'} else d)[name]
+    return Config(_wrap(rec))
 
 
 def test_base_files_and_merge_semantics(tmp_path):
@@ -28,11 +38,9 @@ def test_base_files_and_merge_semantics(tmp_path):
         Config.fromfile(str(bad))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference tree not present on this box')
 @pytest.mark.parametrize('name', ['DHD-S', 'DHD-M', 'DHD-L'])
 def test_reference_configs_load_unchanged(name):
-    from dhd_amd.config import Config
-    cfg = Config.fromfile(os.path.join(REF_CFG, name + '.py'))
+    cfg = reference_config(name)
     assert cfg.plugin is True and cfg.plugin_dir == 'projects/mmdet3d_plugin/'
     assert cfg.dist_params.backend == 'nccl' and cfg.optimizer.type == 'AdamW' and cfg.optimizer.lr == 2e-4
     assert cfg.data.train.type == 'NuScenesDatasetOccpancy' and cfg.runner.max_epochs == 24
@@ -42,12 +50,10 @@ def test_reference_configs_load_unchanged(name):
     assert cfg.data.samples_per_gpu == {'DHD-S': 4, 'DHD-M': 3, 'DHD-L': 2}[name]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference tree not present on this box')
 def test_dhd_s_config_builds_the_detector_and_matches_the_packaged_copy():
     import dhd_amd
-    from dhd_amd.config import Config
     from dhd_amd.detector import dhd_s_model_cfg
-    cfg = Config.fromfile(os.path.join(REF_CFG, 'DHD-S.py'))
+    cfg = reference_config('DHD-S')
     ours = dhd_s_model_cfg()
     ref = cfg.model
     assert set(ref) == set(ours)
@@ -62,17 +68,15 @@ def test_dhd_s_config_builds_the_detector_and_matches_the_packaged_copy():
             assert a == b, k
     model = dhd_amd.build_detector(cfg.model)
     assert type(model).__name__ == 'DHD' and type(model.img_view_transformer).__name__ == 'MGHS'
-    m = dhd_amd.build_neck(Config.fromfile(os.path.join(REF_CFG, 'DHD-M.py')).model.img_view_transformer)
+    m = dhd_amd.build_neck(reference_config('DHD-M').model.img_view_transformer)
     assert type(m).__name__ == 'MGHS_Stereo' and m.D == 88 and m.collapse_z is False
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference tree not present on this box')
 def test_dhd_m_config_builds_the_temporal_stereo_detector():
     """projects/configs/DHD/DHD-M.py (DHD_stereo + MGHS_Stereo, ResNet-50, one adjacent frame + one stereo
     reference frame) builds unchanged; parameter names follow the reference's attribute names."""
     import dhd_amd
-    from dhd_amd.config import Config
-    cfg = Config.fromfile(os.path.join(REF_CFG, 'DHD-M.py'))
+    cfg = reference_config('DHD-M')
     m = dhd_amd.build_detector(cfg.model)
     assert type(m).__name__ == 'DHD_stereo' and m.num_frame == 3 and m.temporal_frame == 2 and m.extra_ref_frames == 1
     assert m.pre_process and not m.align_after_view_transfromation
@@ -93,13 +97,11 @@ def test_dhd_m_config_builds_the_temporal_stereo_detector():
             assert b == ref[k], k
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference tree not present on this box')
 def test_dhd_l_config_builds_with_the_swin_backbone():
     """projects/configs/DHD/DHD-L.py (Swin-B, 512 x 1408 images, FPN_LSS necks) builds unchanged."""
     import dhd_amd
-    from dhd_amd.config import Config
     from dhd_amd.detector import dhd_l_model_cfg
-    cfg = Config.fromfile(os.path.join(REF_CFG, 'DHD-L.py'))
+    cfg = reference_config('DHD-L')
     m = dhd_amd.build_detector(cfg.model)
     assert type(m).__name__ == 'DHD_stereo' and type(m.img_backbone).__name__ == 'SwinTransformer'
     assert sum(p.numel() for p in m.img_backbone.parameters()) == 86_879_608   # Swin-B, 12 x 12 windows, norms of stages 2 and 3 only
