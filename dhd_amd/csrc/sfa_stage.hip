@@ -8,17 +8,10 @@
 //
 // The two 1x1 convolutions are (C x C) x (C x B*HW) GEMMs on NCHW data (six of them per forward + backward).  They run on the
 // matrix cores with everything element-wise FUSED into the operand path, so no intermediate but y1 and y2 is ever stored.
-// Precision per call (dhd_sfa_weights.gemm / storage_dtype, include/dhd_amd.h) and the kernel family that serves it:
-//   bf16x3 (default) bf16 MFMA on a two-way split of every float32 operand, three products per a*b:
-//                    C = 128 / 256 (DHD-S / DHD-L: SFA(512, 256)): pw_gemm_cu (sfa_gemm_cu.h: one CU per pixel tile, weights in
-//                    registers); C = 512 (DHD-M): pw_gemm_res<2> (sfa_gemm_res.h); weight gradients: pw_wgrad3 (this file)
-//   bf16x6           exact three-way split, six products (float32-level accuracy): pw_gemm_res<3> at C = 128 / 256, pw_gemm6 at
-//                    C = 512 and beyond (sfa_gemm_streamed.h); pw_wgrad6
-//   f32              v_mfma_f32_32x32x2_f32, the float32 reference point of the precision table: pw_gemm / pw_wgrad (sfa_gemm_streamed.h)
-//   half storage     x / y1 / y2 / g2 / g1 / du in fp16 or bf16, single half products with float32 accumulation -- the form under
-//                    autocast: pw_gemm_cuh / pw_wgrad_h (sfa_half.h), element-wise passes and host side in sfa_stage_half.h
+// Precision per call (dhd_sfa_weights.gemm / storage_dtype, include/dhd_amd.h): bf16x3 (default), bf16x6, f32, or half storage.
+// make_plan (host side, below) states which kernel family serves each precision and channel count.
 // This file: the small dense pieces (channel mean -> fc -> a), BatchNorm statistics and coefficient tables, the fused blends,
-// pw_wgrad3 + the deterministic partial reduction, and the host side of the float32-storage operator.
+// pw_wgrad3 + the deterministic partial reduction, and the host side of the operator for every storage type.
 // Common structure of the GEMMs:
 //   * forward / dgrad: the activation operand passes through a per-(sample,channel) affine prologue act(c0*in0 + c1*in1 + c2)
 //     -- which is blend1 (in0,in1 = x_bev,x_voxel), BatchNorm+ReLU (in0 = y1) or BatchNorm-backward (in0,in1 = g,y); epilogue:
@@ -31,6 +24,8 @@
 // Forward reads x three times and y1/y2 twice; nothing is transposed, there is no NHWC detour.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "sfa_gemm_cu.h"
 #include "sfa_half.h"
 #include "sfa_mfma.h"
@@ -42,9 +37,6 @@ namespace {
 constexpr int kEwBlock = 256;     // element-wise / reduction kernels
 constexpr int kPlaneChunks = 4;   // blocks per (b, c) plane
 constexpr int kPwBlock = 256;     // pw_gemm: 4 waves
-#ifndef DHD_PW_COT_SEL
-#define DHD_PW_COT_SEL 8
-#endif
 constexpr int kPwStep = 16;       // input channels per weight image / pipeline step
 constexpr int kWgBlock = 512;     // pw_wgrad: 8 waves
 constexpr int kWgStride = 33;     // LDS row stride of a 32-pixel operand row (conflict-free column reads)
@@ -1004,125 +996,85 @@ __global__ __launch_bounds__(kEwBlock) void wgrad_reduce_kernel(const float* __r
 // host side
 // ------------------------------------------------------------------------------------------------
 
-inline size_t align_up(size_t v) { return (v + 63) & ~(size_t)63; }  // in floats: 256-byte sections
+#include "sfa_stage_half.h"   // the element-wise kernels of the half-storage form
 
-struct SavedLayout {
-  size_t s, h, a1, tab_a, mean1, rstd1, scsh1, tab1, mean2, rstd2, scsh2, loc1, loc2, tick, wp1t, wp2t, mask, y1, y2, total;
-};
-constexpr int kTickWords = 64;   // arrival counters besides the per-channel ones (see saved_layout)
-SavedLayout saved_layout(int b, int c, int hw, int r) {
-  SavedLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o += align_up(n); return at; };
-  L.s = take((size_t)b * 2 * c);
-  L.h = take((size_t)b * r);
-  L.a1 = take((size_t)b * c);
-  L.tab_a = take((size_t)b * 3 * c);
-  L.mean1 = take(c); L.rstd1 = take(c); L.scsh1 = take(2 * c); L.tab1 = take((size_t)b * 3 * c);
-  L.mean2 = take(c); L.rstd2 = take(c); L.scsh2 = take(2 * c);
-  L.loc1 = take(2 * (2 * (size_t)c + 1)); L.loc2 = take(2 * (2 * (size_t)c + 1));   // (2C + 1) doubles each: this rank's shifted sums + count (phased calls)
-  // arrival counters of the kernels that finish their own reductions (BnTail): [c] BatchNorm-2 backward | [c] BatchNorm-1
-  // backward | kTickWords others; zeroed by the forward (fc_forward_kernel), left at zero by every kernel that uses them
-  L.tick = take(2 * (size_t)c + kTickWords);
-  L.wp1t = take(2 * (size_t)c * c); L.wp2t = take(2 * (size_t)c * c);   // transposed weight images, packed by the forward for the backward
-  // ReLU pass bits, one per activation: a word per (32 pixels, channel), [sample][wave tile][channel] (resident / streamed
-  // kernels), or 16-bit words in the staging lanes' order (cu kernels, sfa_gemm_cu.h: cu_mask_words)
-  L.mask = take((size_t)b * c * ((hw + 31) / 32));
-  L.y1 = take((size_t)b * c * hw);
-  L.y2 = take((size_t)b * c * hw);
-  L.total = o;
-  return L;
-}
-
-struct ScratchLayout {
-  size_t wp1, wp2, part, da1, da2, tab_g2, tab_g1, dpre2, dh, ds, mean_part, stat_part, g2, g1, du, wpart, total;
-};
-ScratchLayout scratch_layout(int b, int c, int hw, int r) {
-  ScratchLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o += align_up(n); return at; };
-  const size_t cc = (size_t)c * c, plane = (size_t)b * c * hw;
-  L.wp1 = take(2 * cc); L.wp2 = take(2 * cc);  // f32 images: cc, bf16x6 images: 1.5 cc (the transposed ones: SavedLayout)
-  L.part = take((size_t)b * kPlaneChunks * 2 * c);
-  L.stat_part = take((size_t)b * ((hw + 31) / 32 + 64) * 2 * c);   // a row per (sample, wave tile), or per wave of every launch (<= tiles + 63 each)
-  L.da1 = take((size_t)b * kPlaneChunks * c);
-  L.da2 = take((size_t)b * kPlaneChunks * c);
-  L.tab_g2 = take((size_t)b * 3 * c);
-  L.tab_g1 = take((size_t)b * 3 * c);
-  L.dpre2 = take((size_t)b * c);
-  L.dh = take((size_t)b * r);
-  L.ds = take((size_t)b * 2 * c);
-  L.mean_part = take((size_t)b * 2 * c * kPlaneChunks);
-  L.g2 = take(plane); L.g1 = take(plane); L.du = take(plane);
-  L.wpart = take((size_t)kWgWorkers * cc);
-  L.total = o;
-  return L;
-}
-
-// output channels per block = 32 * cot
-inline int pw_cot(int c) { return (DHD_PW_COT_SEL == 8 && c % 256 == 0) ? 8 : 4; }
+constexpr int kTickWords = 64;                     // arrival counters besides the per-channel ones (see saved_layout)
+constexpr int kResWaves = 8;                       // waves per resident workgroup
+constexpr size_t kResTrBytes = (size_t)kResWaves * 16 * kResTrPitch * sizeof(float);  // store patches of the waves
+constexpr size_t kLdsBytes = 160 * 1024;           // per-CU LDS of gfx950
+constexpr size_t kResWeightMax = 128 * 1024;       // budget for the weight fragments
+template <int N> using IntC = std::integral_constant<int, N>;
 
 // (one sample of the input, 2 C hw floats, must stay below 4 GiB: the GEMMs address a sample through 32-bit buffer offsets)
 inline bool stage_supported(int c, int hw) {
   return (c == 128 || (c > 0 && c % 256 == 0)) && hw > 0 && (hw & 3) == 0 && (size_t)2 * c * hw * sizeof(float) <= 0xFFFFFFFFull;
 }
 
-// hipFuncSetAttribute is not a stream operation: doing it on every launch breaks stream capture (HIP graphs),
-// so each kernel instantiation raises its dynamic-LDS limit once per device, on first use.
+// C = 128 / 256 (the weight fragments of 32 channels x all K fit a wave's registers, one wave per 32 channels) and whole
+// 16-byte vectors of the half type per plane
+inline bool half_storage_supported(int c, int hw) { return (c == 128 || c == 256) && hw > 0 && (hw & 7) == 0 && stage_supported(c, hw); }
+
+// Workspace layouts in BYTES, every section 256-byte aligned: the small float32 tables first, then the tensors in the storage
+// type.  Besides the element size, the storage type sets the size of the weight images (float32 storage: f32 images take
+// c^2 floats, bf16x6 images 1.5 c^2 -- room for 2 c^2 floats is kept; half storage: c^2 halves), of the ReLU pass bits and of
+// the GEMM epilogues' statistics rows.
+struct SavedLayout {
+  size_t s, h, a1, tab_a, mean1, rstd1, scsh1, tab1, mean2, rstd2, scsh2, loc1, loc2, tick, wp1t, wp2t, mask, y1, y2, total;
+};
+inline SavedLayout saved_layout(int b, int c, int hw, int r, int storage) {
+  const bool half = storage != DHD_F32;
+  const size_t cc = (size_t)c * c, plane = (size_t)b * c * hw * (half ? 2 : 4);
+  SavedLayout L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  auto f = [&](size_t n) { return take(n * sizeof(float)); };
+  L.s = f((size_t)b * 2 * c); L.h = f((size_t)b * r); L.a1 = f((size_t)b * c); L.tab_a = f((size_t)b * 3 * c);
+  L.mean1 = f(c); L.rstd1 = f(c); L.scsh1 = f(2 * c); L.tab1 = f((size_t)b * 3 * c);
+  L.mean2 = f(c); L.rstd2 = f(c); L.scsh2 = f(2 * c);
+  // (2C + 1) doubles each: this rank's shifted sums + count (phased calls)
+  L.loc1 = take((2 * (size_t)c + 1) * sizeof(double)); L.loc2 = take((2 * (size_t)c + 1) * sizeof(double));
+  // arrival counters of the kernels that finish their own reductions (BnTail): [c] BatchNorm-2 backward | [c] BatchNorm-1
+  // backward | kTickWords others; zeroed by the forward (fc_forward_kernel), left at zero by every kernel that uses them
+  L.tick = f(2 * (size_t)c + kTickWords);
+  // transposed weight images, packed by the forward for the backward
+  L.wp1t = take(half ? 2 * cc : 8 * cc); L.wp2t = take(half ? 2 * cc : 8 * cc);
+  // ReLU pass bits, one per activation: a word per (32 pixels, channel), [sample][wave tile][channel] (resident / streamed
+  // kernels), 16-bit words in the staging lanes' order (cu kernels, sfa_gemm_cu.h: cu_mask_words), or cuh_mask_words (sfa_half.h)
+  L.mask = take((half ? cuh_mask_words(b, c, hw) : (size_t)b * c * ((hw + 31) / 32)) * sizeof(unsigned));
+  L.y1 = take(plane); L.y2 = take(plane);
+  L.total = o;
+  return L;
+}
+
+struct ScratchLayout {
+  size_t wp1, wp2, part, stat_part, da1, da2, tab_g2, tab_g1, dpre2, dh, ds, mean_part, g2, g1, du, wpart, total;
+};
+inline ScratchLayout scratch_layout(int b, int c, int hw, int r, int storage) {
+  const bool half = storage != DHD_F32;
+  const size_t cc = (size_t)c * c, plane = (size_t)b * c * hw * (half ? 2 : 4);
+  ScratchLayout L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  auto f = [&](size_t n) { return take(n * sizeof(float)); };
+  L.wp1 = take(half ? 2 * cc : 8 * cc); L.wp2 = take(half ? 2 * cc : 8 * cc);
+  L.part = f((size_t)b * kPlaneChunks * 2 * c);
+  // GEMM statistics rows: float32 storage a row per (sample, wave tile), or per wave of every launch (<= tiles + 63 each); half
+  // storage one per workgroup of every launch (>= 8 samples per launch, <= 1024 CUs)
+  L.stat_part = f((half ? (size_t)(b / 8 + 2) * 1024 : (size_t)b * ((hw + 31) / 32 + 64)) * 2 * c);
+  L.da1 = f((size_t)b * kPlaneChunks * c); L.da2 = f((size_t)b * kPlaneChunks * c);
+  L.tab_g2 = f((size_t)b * 3 * c); L.tab_g1 = f((size_t)b * 3 * c);
+  L.dpre2 = f((size_t)b * c); L.dh = f((size_t)b * r); L.ds = f((size_t)b * 2 * c);
+  L.mean_part = f((size_t)b * 2 * c * kPlaneChunks);
+  L.g2 = take(plane); L.g1 = take(plane); L.du = take(plane);
+  L.wpart = f((size_t)kWgWorkers * cc);
+  L.total = o;
+  return L;
+}
+
 inline int device_index() {
   int d = 0;
   (void)hipGetDevice(&d);
   return d < 0 || d >= 64 ? 0 : d;
-}
-#define DHD_LDS_ATTR_ONCE(kern, bytes)                                                                              \
-  do {                                                                                                              \
-    static bool done__[64] = {};                                                                                    \
-    const int dev__ = device_index();                                                                               \
-    if (!done__[dev__]) {                                                                                           \
-      DHD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                  (int)(bytes)));                                                                   \
-      done__[dev__] = true;                                                                                         \
-    }                                                                                                               \
-  } while (0)
-
-// GEMM precision of the current call (dhd_sfa_weights.gemm), carried in a thread-local for the duration of the entry
-// point -- per call, nothing process-wide.  Internal numbering:
-//   0  f32 MFMA (pw_gemm / pw_wgrad)                                                    DHD_SFA_GEMM_F32
-//   1  bf16x6: weights resident in LDS (pw_gemm_res<3>) where that form covers the channel count, else streamed per
-//      pixel tile (pw_gemm6, with the 128-channel tail launch); bit-identical results      DHD_SFA_GEMM_BF16X6
-//   3  bf16x3, weights resident in LDS (pw_gemm_res<2>): three products per a*b, relative error <= 3 * 2^-18 per
-//      product.  DEFAULT: measured against float64 at (2,512,200,200) the stage output is off by 2.2e-5 (bf16x6:
-//      1.2e-6, plain PyTorch fp32: 1.35e-6), well inside the 1e-3 bar of the path.         DHD_SFA_GEMM_BF16X3
-thread_local int g_gemm_mode = 3;
-inline int set_call_mode(int gemm) {
-  switch (gemm) {
-    case DHD_SFA_GEMM_DEFAULT: case DHD_SFA_GEMM_BF16X3: g_gemm_mode = 3; return DHD_OK;
-    case DHD_SFA_GEMM_BF16X6: g_gemm_mode = 1; return DHD_OK;
-    case DHD_SFA_GEMM_F32: g_gemm_mode = 0; return DHD_OK;
-    default: return DHD_EINVAL;
-  }
-}
-inline bool mode_resident() { return g_gemm_mode == 1 || g_gemm_mode == 3; }
-inline int mode_terms() { return g_gemm_mode == 3 ? 2 : 3; }
-
-constexpr int kResWaves = 8;                       // waves per resident workgroup
-constexpr size_t kResTrBytes = (size_t)kResWaves * 16 * kResTrPitch * sizeof(float);  // store patches of the waves
-constexpr size_t kLdsBytes = 160 * 1024;           // per-CU LDS of gfx950
-constexpr size_t kResWeightMax = 128 * 1024;       // budget for the weight fragments
-// 32-channel output tiles per resident workgroup: the largest of 4 / 2 / 1 whose fragments fit; 0 = does not fit
-inline int res_cob(int c, int nt) {
-  for (int cob = 4; cob >= 1; cob >>= 1)
-    if (32 * cob <= c && (size_t)(c / 16) * cob * nt * 1024 <= kResWeightMax) return cob;
-  return 0;
-}
-inline bool res_supported(int c) {
-  if (!mode_resident() || (c != 128 && c != 256 && c != 512)) return false;
-  const int nt = mode_terms(), cob = res_cob(c, nt);
-  if (c == 128) return cob == 4;
-  if (c == 256) return nt == 2 ? (cob == 4 || cob == 2) : cob == 2;
-  // C = 512: bf16x3 with teams of 8 still beats the streamed form (2.85 vs 3.43 ms per stage at B = 3); bf16x6 would need
-  // teams of 16 (4.23 ms) and stays on the streamed kernels (bit-identical results)
-  return nt == 2 && cob == 2;
 }
 
 int cu_count() {
@@ -1132,20 +1084,148 @@ int cu_count() {
   return n[dev];
 }
 
-// One-CU-per-pixel-tile kernels (sfa_gemm_cu.h): the default precision (bf16x3) at the channel counts whose weight fragments
-// fit the register file of a CU -- C = 256 (8 waves x 32 channels) and C = 128 (4 waves).  C = 512 (1 MB of fragments) and the
-// bf16x6 precision (three parts) stay on the LDS-resident / streamed kernels.
-inline bool cu_supported(int c) { return g_gemm_mode == 3 && (c == 128 || c == 256); }
+// hipFuncSetAttribute is not a stream operation: doing it on every launch breaks stream capture (HIP graphs), so each kernel
+// raises its dynamic-LDS limit once per device, on its first launch.  The flag belongs to the kernel (many share a signature).
+template <auto Kern>
+int lds_limit_once(size_t bytes) {
+  static bool done[64] = {};
+  const int dev = device_index();
+  if (!done[dev]) {
+    DHD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done[dev] = true;
+  }
+  return DHD_OK;
+}
+template <auto Kern, class... Args>
+int launch_lds(dim3 grid, dim3 block, size_t shmem, size_t limit, hipStream_t st, Args... args) {
+  if (int rc = lds_limit_once<Kern>(limit); rc != DHD_OK) return rc;
+  hipLaunchKernelGGL(Kern, grid, block, shmem, st, args...);
+  DHD_LAUNCH_CHECK();
+  return DHD_OK;
+}
 
-int launch_pw_gemm_cu(const float* in0, const float* in1, size_t in_bstride, int in_channels, const float* coef, bool relu, const float* wp,
-                      const float* bias, unsigned* relu_mask, float* stat_part, float* y, int epi, int b, int c, int hw, hipStream_t st,
-                      int* stat_rows) {
-  const int waves = c == 256 ? 8 : 4;
-  const int max_b = cu_max_batch(c, waves);
+// 32-channel output tiles per resident workgroup: the largest of 4 / 2 / 1 whose fragments fit; 0 = does not fit
+inline int res_cob(int c, int nt) {
+  for (int cob = 4; cob >= 1; cob >>= 1)
+    if (32 * cob <= c && (size_t)(c / 16) * cob * nt * 1024 <= kResWeightMax) return cob;
+  return 0;
+}
+
+// The kernels of one call, chosen once per entry point by make_plan and passed to every launcher.
+enum class Gemm { cu, cuh, res, streamed6, f32 };   // forward / data-gradient GEMMs
+enum class Wgrad { w3, w6, f32, half };              // weight gradients
+enum class Pack { cu, res, six, f32, cuh };          // weight images (cu / res / cuh: one launch with the channel means)
+struct Plan {
+  int storage;        // DHD_F32, or the half type every tensor of the stage is stored in
+  Gemm gemm;
+  Wgrad wgrad;
+  Pack pack;
+  int nt, cob;        // bf16 parts per operand (2: bf16x3, 3: bf16x6) and 32-channel tiles per resident workgroup (cu / res images)
+  int cot;            // streamed6 / f32: 32-channel output tiles per workgroup
+  bool fused_stats;   // training-mode BatchNorm sums come out of the GEMM epilogues (else moments_kernel)
+};
+
+// The precision of a call (dhd_sfa_weights.gemm / storage_dtype, include/dhd_amd.h) and the kernel family that serves it.
+// Error codes in the order the entry points have always checked them.
+int make_plan(const dhd_sfa_weights* w, int c, int hw, Plan* p) {
+  *p = Plan{};
+  switch (w->gemm) {
+    // bf16x3 (default): bf16 MFMA on a two-way split of every float32 operand, three products per a*b, relative error
+    // <= 3 * 2^-18 per product.  Measured against float64 at (2,512,200,200) the stage output is off by 2.2e-5 (bf16x6:
+    // 1.2e-6, plain PyTorch fp32: 1.35e-6), well inside the 1e-3 bar of the path.
+    case DHD_SFA_GEMM_DEFAULT: case DHD_SFA_GEMM_BF16X3: p->nt = 2; break;
+    // bf16x6: exact three-way split, six products (float32-level accuracy)
+    case DHD_SFA_GEMM_BF16X6: p->nt = 3; break;
+    // f32: v_mfma_f32_32x32x2_f32, the float32 reference point of the precision table
+    case DHD_SFA_GEMM_F32: p->nt = 0; break;
+    default: return DHD_EINVAL;
+  }
+  if (w->io_dtype != DHD_F32 && w->io_dtype != DHD_F16 && w->io_dtype != DHD_BF16) return DHD_EINVAL;
+  p->storage = w->storage_dtype;
+  if (p->storage != DHD_F32) {
+    // half storage (what an autocast region gets): x / y1 / y2 / g2 / g1 / du in fp16 or bf16 (== io_dtype), single half
+    // products with float32 accumulation whatever the precision: pw_gemm_cuh / pw_wgrad_h (sfa_half.h), 64-pixel tiles
+    if (p->storage != DHD_F16 && p->storage != DHD_BF16) return DHD_EINVAL;
+    if (w->io_dtype != p->storage) return DHD_EINVAL;
+    if (!half_storage_supported(c, hw)) return DHD_EUNSUPPORTED;
+    p->gemm = Gemm::cuh; p->wgrad = Wgrad::half; p->pack = Pack::cuh;
+    p->fused_stats = w->training != 0;
+    return DHD_OK;
+  }
+  p->fused_stats = w->training && p->nt > 0;
+  p->cob = p->nt > 0 ? res_cob(c, p->nt) : 0;
+  p->cot = c % 256 == 0 ? 8 : 4;
+  // weight gradients follow the precision alone: pw_wgrad3 (this file), pw_wgrad6 / pw_wgrad (sfa_gemm_streamed.h)
+  p->wgrad = p->nt == 2 ? Wgrad::w3 : p->nt == 3 ? Wgrad::w6 : Wgrad::f32;
+  if (p->nt == 2 && (c == 128 || c == 256)) {
+    // bf16x3 at C = 128 / 256 (DHD-S / DHD-L: SFA(512, 256)): pw_gemm_cu (sfa_gemm_cu.h: one CU per pixel tile, weights in
+    // registers, 8 waves x 32 channels or 4 waves).  C = 512 (1 MB of fragments) does not fit the register file of a CU.
+    p->gemm = Gemm::cu; p->pack = Pack::cu;
+  } else if ((p->nt == 2 && c == 512) || (p->nt == 3 && c <= 256)) {
+    // weights resident in LDS (pw_gemm_res, sfa_gemm_res.h): bf16x6 at C = 128 (4 tiles per workgroup) / 256 (2), bf16x3 at
+    // C = 512 (2): teams of 8 still beat the streamed form (2.85 vs 3.43 ms per stage at B = 3).  bf16x6 at C = 512 would need
+    // teams of 16 (4.23 ms) and stays on the streamed kernels.
+    p->gemm = Gemm::res; p->pack = Pack::res;
+  } else if (p->nt > 0) {
+    // weights streamed per pixel tile, bf16x6 operands (pw_gemm6 + its 128-channel tail launch, sfa_gemm_streamed.h): bf16x6 at
+    // C >= 512 and bf16x3 at C >= 768 -- the latter has no streamed GEMM of its own, and keeps the bf16x3 weight gradient
+    p->gemm = Gemm::streamed6; p->pack = Pack::six;
+  } else {
+    p->gemm = Gemm::f32; p->pack = Pack::f32;   // pw_gemm / pw_wgrad (sfa_gemm_streamed.h)
+  }
+  return DHD_OK;
+}
+
+// The four GEMMs of a call and, as template arguments, the variant of the kernels that serves each: conv1 (blend1 prologue over
+// x_bev / x_voxel, bias epilogue), conv2 (BatchNorm + ReLU prologue, records the ReLU pass bits), the data gradients through
+// conv2 (BatchNorm-backward prologue over g2 / y2, ReLU mask epilogue) and through conv1.  A weight gradient's second operand is
+// the input of conv1 or conv2 and takes that GEMM's prologue.
+enum Op { kConv1, kConv2, kDgrad2, kDgrad1 };
+template <int OP>
+struct Variant {
+  static constexpr bool two = OP != kConv2;     // two inputs
+  static constexpr bool relu = OP == kConv2;    // ReLU after the prologue
+  static constexpr int epi = OP == kDgrad2 ? 1 : OP == kDgrad1 ? 2 : 0;   // 0 forward (+bias), 1 dgrad with ReLU mask, 2 dgrad plain
+  static constexpr bool rec = OP == kConv2;     // records the ReLU pass bits
+};
+template <class F>
+int with_op(Op op, F&& f) {
+  switch (op) {
+    case kConv1: return f(Variant<kConv1>{});
+    case kConv2: return f(Variant<kConv2>{});
+    case kDgrad2: return f(Variant<kDgrad2>{});
+    case kDgrad1: return f(Variant<kDgrad1>{});
+  }
+  return DHD_EUNSUPPORTED;
+}
+
+// One forward / data-gradient GEMM: y = W . act(c0*in0 + c1*in1 + c2), per-(sample, channel) coefficients
+template <class TS>
+struct GemmCall {
+  Op op;
+  const TS* in0;
+  const TS* in1;             // nullptr for conv2
+  size_t in_bstride;
+  int in_channels;
+  const float* coef;
+  const void* wp;            // packed weight image
+  const float* bias;
+  unsigned* mask;            // ReLU pass bits: written by conv2, read by dgrad 2
+  float* stat_part;          // BatchNorm sums rows (fused statistics), or nullptr
+  TS* y;
+  const TS* aux;             // f32 dgrad 2: y1 and BatchNorm-1, the ReLU mask recomputed
+  const float* aux_scsh;
+};
+
+// One-CU-per-pixel-tile kernels: pw_gemm_cu (float32 storage, sfa_gemm_cu.h) and pw_gemm_cuh (half storage, sfa_half.h)
+template <class TS>
+int launch_gemm_cu(const GemmCall<TS>& g, int b, int c, int hw, hipStream_t st, int* stat_rows) {
+  constexpr bool kHalf = !std::is_same<TS, float>::value;
+  const int waves = c / 32;
+  const int max_b = kHalf ? cuh_max_batch(c, waves) : cu_max_batch(c, waves);
   if (max_b < 1) return DHD_EUNSUPPORTED;
-  const bool two = in1 != nullptr;
-  const unsigned in_bytes = (unsigned)((size_t)in_channels * hw * sizeof(float));
-  const int nwt = (hw + 31) / 32;
+  const unsigned in_bytes = (unsigned)((size_t)g.in_channels * hw * sizeof(TS));
+  const int nwt = kHalf ? (hw + kCuhTile - 1) / kCuhTile : (hw + 31) / 32;
   int cus = cu_count();
   if (cus <= 0) cus = 256;
   int rows_done = 0;
@@ -1153,79 +1233,47 @@ int launch_pw_gemm_cu(const float* in0, const float* in1, size_t in_bstride, int
     const int nb = b - b0 < max_b ? b - b0 : max_b;
     const long total = (long)nb * nwt;
     const int grid = (int)(total < cus ? total : cus);
-    const size_t shmem = cu_lds_bytes(c, waves, nb);
-    const float* i0 = in0 + (size_t)b0 * in_bstride;
-    const float* i1 = two ? in1 + (size_t)b0 * in_bstride : nullptr;
-    const float* cf = coef + (size_t)b0 * 3 * c;
-    unsigned* rm = relu_mask ? relu_mask + cu_mask_words(b0, c, hw) : nullptr;
-    float* sp = stat_part ? stat_part + (size_t)rows_done * 2 * c : nullptr;
+    const size_t shmem = kHalf ? cuh_lds_bytes(c, waves, nb) : cu_lds_bytes(c, waves, nb);
+    const TS* i0 = g.in0 + (size_t)b0 * g.in_bstride;
+    const TS* i1 = g.in1 ? g.in1 + (size_t)b0 * g.in_bstride : nullptr;
+    const float* cf = g.coef + (size_t)b0 * 3 * c;
+    const u32x4* wp = static_cast<const u32x4*>(g.wp);
+    unsigned* rm = g.mask ? g.mask + (kHalf ? cuh_mask_words(b0, c, hw) : cu_mask_words(b0, c, hw)) : nullptr;
+    float* sp = g.stat_part ? g.stat_part + (size_t)rows_done * 2 * c : nullptr;
     rows_done += grid;                                   // one statistics row per workgroup
-    float* yo = y + (size_t)b0 * c * hw;
-    // <KCN, WAVES, TWO_IN, RELU, EPI, RECORD, AUX = nt loads, R = 1, NACC = 1, ABL = 0, SAUX = 0, PP = ping-pong, BPF = 0, EORD>,
-    // contiguous tile ranges.  EORD: with two inputs the epilogue goes before the staging (which waits for twice the loads), with
-    // one input after it -- measured either way (experiments/gemm_cu_bench.hip): 100 vs 107 us (conv1), 96 vs 97 (dgrad), 82 vs 76 (conv2)
-#define DHD_CU(KCN, WAVES, TWO, RELU, EPI, REC)                                                                          \
-  do {                                                                                                                \
-    auto kern = pw_gemm_cu_kernel<KCN, WAVES, TWO, RELU, EPI, REC, 2, 1, 1, 0, 0, true, 0, (TWO) ? 1 : 0>;           \
-    DHD_LDS_ATTR_ONCE(kern, kLdsBytes);                                                                               \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), shmem, st, i0, i1, in_bstride, in_bytes, cf,               \
-                       reinterpret_cast<const u32x4*>(wp), bias, rm, sp, yo, hw, nb, 1);                              \
-  } while (0)
-#define DHD_CU_V(KCN, WAVES)                                                                       \
-  do {                                                                                             \
-    if (epi == 0 && two && !relu) DHD_CU(KCN, WAVES, true, false, 0, false);                       \
-    else if (epi == 0 && !two && relu && rm) DHD_CU(KCN, WAVES, false, true, 0, true);             \
-    else if (epi == 0 && !two && relu) DHD_CU(KCN, WAVES, false, true, 0, false);                  \
-    else if (epi == 1 && two && !relu) DHD_CU(KCN, WAVES, true, false, 1, false);                  \
-    else if (epi == 2 && two && !relu) DHD_CU(KCN, WAVES, true, false, 2, false);                  \
-    else return DHD_EUNSUPPORTED;                                                                  \
-  } while (0)
-    if (c == 256) DHD_CU_V(16, 8);
-    else DHD_CU_V(8, 4);
-#undef DHD_CU_V
-#undef DHD_CU
-    DHD_LAUNCH_CHECK();
+    TS* yo = g.y + (size_t)b0 * c * hw;
+    // EORD: with two inputs the epilogue goes before the staging (which waits for twice the loads), with one input after it --
+    // measured either way (experiments/gemm_cu_bench.hip): 100 vs 107 us (conv1), 96 vs 97 (dgrad), 82 vs 76 (conv2).
+    // float32: <KCN, WAVES, TWO_IN, RELU, EPI, RECORD, AUX = nt loads, R = 1, NACC = 1, ABL = 0, SAUX = 0, PP = ping-pong, BPF = 0,
+    // EORD>, contiguous tile ranges
+    const int rc = with_op(g.op, [&](auto v) {
+      using V = decltype(v);
+      auto run = [&](auto kcn) {
+        constexpr int KCN = decltype(kcn)::value, WAVES = KCN / 2, EORD = V::two ? 1 : 0;
+        if constexpr (kHalf)
+          return launch_lds<pw_gemm_cuh_kernel<TS, KCN, WAVES, V::two, V::relu, V::epi, V::rec, EORD>>(
+              dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb);
+        else
+          return launch_lds<pw_gemm_cu_kernel<KCN, WAVES, V::two, V::relu, V::epi, V::rec, 2, 1, 1, 0, 0, true, 0, EORD>>(
+              dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb, 1);
+      };
+      return c == 256 ? run(IntC<16>{}) : run(IntC<8>{});
+    });
+    if (rc != DHD_OK) return rc;
   }
   if (stat_rows) *stat_rows = rows_done;
   return DHD_OK;
 }
 
-int launch_pack(const float* w, int transpose, float* packed, int c, hipStream_t st, const float* w2 = nullptr,
-                float* packed2 = nullptr) {
-  const int cot = pw_cot(c);
-  if (res_supported(c)) {
-    const int nt = mode_terms();
-    hipLaunchKernelGGL(pack_weight_res_kernel, dim3(dhd_cdiv((c / 32) * (c / 16) * 64, kEwBlock), w2 ? 2 : 1), dim3(kEwBlock), 0, st, w,
-                       w2, transpose, reinterpret_cast<u32x4*>(packed), reinterpret_cast<u32x4*>(packed2), c, res_cob(c, nt), nt);
-    DHD_LAUNCH_CHECK();
-    return DHD_OK;
-  }
-  if (w2) {   // the streamed / f32 forms pack one weight per launch
-    const int rc = launch_pack(w, transpose, packed, c, st);
-    return rc != DHD_OK ? rc : launch_pack(w2, transpose, packed2, c, st);
-  }
-  if (g_gemm_mode >= 1)
-    hipLaunchKernelGGL(pack_weight6_kernel, dim3(dhd_cdiv((c / 32) * (c / 16) * 64, kEwBlock)), dim3(kEwBlock), 0, st, w, transpose,
-                       reinterpret_cast<u32x4*>(packed), c, cot);
-  else
-    hipLaunchKernelGGL(pack_weight_kernel, dim3(dhd_cdiv(c * c, kEwBlock)), dim3(kEwBlock), 0, st, w, transpose, packed, c, cot);
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
-}
-
-// Resident-weights launcher: persistent workgroups, one per CU, teams of C / (32 COB) on one XCD.
-int launch_pw_gemm_res(const float* in0, const float* in1, size_t in_bstride, int in_channels, const float* coef, bool relu, const float* wp,
-                       const float* bias, unsigned* relu_mask, float* stat_part, float* y, int epi, int b, int c, int hw, hipStream_t st,
-                       int* stat_rows) {
+// Resident-weights kernels (pw_gemm_res): persistent workgroups, one per CU, teams of C / (32 COB) on one XCD.
+int launch_gemm_res(const Plan& p, const GemmCall<float>& g, int b, int c, int hw, hipStream_t st, int* stat_rows) {
   int rows_done = 0;   // statistics rows written so far (bf16x3: one per wave of every launch; bf16x6: one per (sample, wave tile))
-  const int nt = mode_terms(), cob = res_cob(c, nt);
-  const int groups = c / (32 * cob);
-  const int kcn = c / 16, nwt = (hw + 31) / 32;
-  const size_t wbytes = (size_t)kcn * cob * nt * 1024;
+  const int groups = c / (32 * p.cob);
+  const int nwt = (hw + 31) / 32;
+  const size_t wbytes = (size_t)(c / 16) * p.cob * p.nt * 1024;
   const int max_b = (int)((kLdsBytes - wbytes - kResTrBytes - 64) / ((size_t)3 * c * sizeof(float)));  // samples whose tables fit next to the weights
   if (max_b < 1) return DHD_EUNSUPPORTED;
-  const bool two = in1 != nullptr;
-  const unsigned in_bytes = (unsigned)((size_t)in_channels * hw * sizeof(float));
+  const unsigned in_bytes = (unsigned)((size_t)g.in_channels * hw * sizeof(float));
   int cus = cu_count();
   if (cus <= 0) cus = 256;
   for (int b0 = 0; b0 < b; b0 += max_b) {
@@ -1237,68 +1285,49 @@ int launch_pw_gemm_res(const float* in0, const float* in1, size_t in_bstride, in
     if (need < nteams) nteams = dhd_cdiv(need, 8) * 8;
     const dim3 grid(nteams * groups);
     const size_t shmem = wbytes + (((size_t)nb * 3 * c + 3) & ~(size_t)3) * sizeof(float) + kResTrBytes;
-    const float* i0 = in0 + (size_t)b0 * in_bstride;
-    const float* i1 = two ? in1 + (size_t)b0 * in_bstride : nullptr;
-    const float* cf = coef + (size_t)b0 * 3 * c;
-    unsigned* rm = relu_mask ? relu_mask + (size_t)b0 * nwt * c : nullptr;
-    float* sp = stat_part ? stat_part + (size_t)rows_done * 2 * c : nullptr;
-    rows_done += nt == 2 ? nteams : (int)total;
-    float* yo = y + (size_t)b0 * c * hw;
-#define DHD_RES(NT, COB, KCN, TWO, RELU, EPI)                                                                            \
-  do {                                                                                                                \
-    auto kern = pw_gemm_res_kernel<NT, COB, KCN, TWO, RELU, EPI, kResWaves, 0, 4>;                                    \
-    DHD_LDS_ATTR_ONCE(kern, kLdsBytes);                                                                               \
-    hipLaunchKernelGGL(kern, grid, dim3(kResWaves * 64), shmem, st, i0, i1, in_bstride, in_bytes, cf,                 \
-                       reinterpret_cast<const u32x4*>(wp), bias, rm, sp, yo, c, hw, nb, groups, nteams);              \
-  } while (0)
-#define DHD_RES_V(NT, COB, KCN)                                                   \
-  do {                                                                            \
-    if (epi == 0 && two && !relu) DHD_RES(NT, COB, KCN, true, false, 0);          \
-    else if (epi == 0 && !two && relu) DHD_RES(NT, COB, KCN, false, true, 0);     \
-    else if (epi == 1 && two && !relu) DHD_RES(NT, COB, KCN, true, false, 1);     \
-    else if (epi == 2 && two && !relu) DHD_RES(NT, COB, KCN, true, false, 2);     \
-    else return DHD_EUNSUPPORTED;                                                 \
-  } while (0)
-    // (terms, tiles per workgroup) by channel count: C = 128: (.,4);  C = 256: x6 (3,2), x3 (2,4) or capped;  C = 512: x6 (3,1), x3 (2,2)
-    if (kcn == 8 && cob == 4 && nt == 2) DHD_RES_V(2, 4, 8);
-    else if (kcn == 8 && cob == 4 && nt == 3) DHD_RES_V(3, 4, 8);
-    else if (kcn == 16 && cob == 4 && nt == 2) DHD_RES_V(2, 4, 16);
-    else if (kcn == 16 && cob == 2 && nt == 2) DHD_RES_V(2, 2, 16);
-    else if (kcn == 16 && cob == 2 && nt == 3) DHD_RES_V(3, 2, 16);
-    else if (kcn == 32 && cob == 2 && nt == 2) DHD_RES_V(2, 2, 32);
-    else if (kcn == 32 && cob == 1 && nt == 3) DHD_RES_V(3, 1, 32);
-    else return DHD_EUNSUPPORTED;
-#undef DHD_RES_V
-#undef DHD_RES
-    DHD_LAUNCH_CHECK();
+    const float* i0 = g.in0 + (size_t)b0 * g.in_bstride;
+    const float* i1 = g.in1 ? g.in1 + (size_t)b0 * g.in_bstride : nullptr;
+    const float* cf = g.coef + (size_t)b0 * 3 * c;
+    const u32x4* wp = static_cast<const u32x4*>(g.wp);
+    unsigned* rm = g.mask ? g.mask + (size_t)b0 * nwt * c : nullptr;
+    float* sp = g.stat_part ? g.stat_part + (size_t)rows_done * 2 * c : nullptr;
+    rows_done += p.nt == 2 ? nteams : (int)total;
+    float* yo = g.y + (size_t)b0 * c * hw;
+    const int rc = with_op(g.op, [&](auto v) {
+      using V = decltype(v);
+      auto run = [&](auto nt, auto cob, auto kcn) {
+        return launch_lds<pw_gemm_res_kernel<decltype(nt)::value, decltype(cob)::value, decltype(kcn)::value, V::two, V::relu, V::epi,
+                                             kResWaves, 0, 4>>(grid, dim3(kResWaves * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride,
+                                                               in_bytes, cf, wp, g.bias, rm, sp, yo, c, hw, nb, groups, nteams);
+      };
+      // (terms, tiles per workgroup) by channel count, as make_plan selects them
+      if (p.nt == 3 && p.cob == 4 && c == 128) return run(IntC<3>{}, IntC<4>{}, IntC<8>{});
+      if (p.nt == 3 && p.cob == 2 && c == 256) return run(IntC<3>{}, IntC<2>{}, IntC<16>{});
+      if (p.nt == 2 && p.cob == 2 && c == 512) return run(IntC<2>{}, IntC<2>{}, IntC<32>{});
+      return (int)DHD_EUNSUPPORTED;
+    });
+    if (rc != DHD_OK) return rc;
   }
   if (stat_rows) *stat_rows = rows_done;
   return DHD_OK;
 }
 
-// in0/in1 prologue GEMM launcher.  epi: 0 forward (+bias), 1 dgrad with ReLU mask, 2 dgrad plain
-int launch_pw_gemm(const float* in0, const float* in1, size_t in_bstride, int in_channels, const float* coef, bool relu, const float* wp,
-                   const float* bias, const float* aux, const float* aux_scsh, unsigned* relu_mask, float* stat_part, float* y, int epi, int b,
-                   int c, int hw, hipStream_t st, int* stat_rows = nullptr) {
-  if (stat_rows) *stat_rows = b * ((hw + 31) / 32);   // the streamed kernels: a row per (sample, wave tile)
-  if (cu_supported(c))
-    return launch_pw_gemm_cu(in0, in1, in_bstride, in_channels, coef, relu, wp, bias, relu_mask, stat_part, y, epi, b, c, hw, st, stat_rows);
-  if (res_supported(c))
-    return launch_pw_gemm_res(in0, in1, in_bstride, in_channels, coef, relu, wp, bias, relu_mask, stat_part, y, epi, b, c, hw, st,
-                              stat_rows);
-  const int cot = pw_cot(c);
+// Streamed-weights kernels: pw_gemm6 (bf16x6 operands) or pw_gemm (f32), 128-pixel tiles, 32 COT output channels per workgroup
+int launch_gemm_streamed(const Plan& p, const GemmCall<float>& g, int b, int c, int hw, hipStream_t st, int* stat_rows) {
+  if (stat_rows) *stat_rows = b * ((hw + 31) / 32);   // a row per (sample, wave tile)
+  const bool six = p.gemm == Gemm::streamed6;
+  const int cot = p.cot;
   const int tps = dhd_cdiv(hw, 32 * (kPwBlock / DHD_WAVE));  // 128-pixel tiles per sample
-  const bool two = in1 != nullptr;
-  const unsigned in_bytes = (unsigned)((size_t)in_channels * hw * sizeof(float));  // one sample of in0 (and of in1, which follows it for x)
-  const size_t shmem = g_gemm_mode >= 1 ? (size_t)2 * cot * 3 * 64 * 16 + (size_t)3 * c * sizeof(float)
-                                        : (size_t)(2 * cot * 512 + 3 * c) * sizeof(float);
+  const unsigned in_bytes = (unsigned)((size_t)g.in_channels * hw * sizeof(float));  // one sample of in0 (and of in1, which follows it for x)
+  const size_t shmem = six ? (size_t)2 * cot * 3 * 64 * 16 + (size_t)3 * c * sizeof(float) : (size_t)(2 * cot * 512 + 3 * c) * sizeof(float);
+  const u32x4* wp = static_cast<const u32x4*>(g.wp);
   // Two 256-channel workgroups fit a CU (accumulators), so the tiles run in rounds of 2 x CUs.  With less
   // than two rounds of work (small batches) a partly filled round is a large share of the time: the tiles
   // beyond the full round go to a second launch of the 128-channel kernel instead (twice the workgroups,
   // three per CU, each about half as long), reading the same packed weights.  Measured -7 % (B = 1) and
   // -3 % (B = 2) on the stage; with more rounds the split gains nothing (B = 4: 1.715 vs 1.714 ms).
   int t_main = tps;
-  if (g_gemm_mode != 0 && cot == 8) {
+  if (six && cot == 8) {
     const int cus = cu_count();
     const long nrb = c / 256, n = (long)b * tps * nrb, slots = 2L * cus;
     if (cus > 0 && n < 2 * slots && n % slots != 0) {
@@ -1310,127 +1339,366 @@ int launch_pw_gemm(const float* in0, const float* in1, size_t in_bstride, int in
   const dim3 grid((t_main == tps ? dhd_cdiv(tps, 8) * 8 : t_main) * (c / (32 * cot)), b);
   const dim3 grid_tail(t_tail8 * (c / 128), b);
   const size_t shmem_tail = (size_t)2 * 4 * 3 * 64 * 16 + (size_t)3 * c * sizeof(float);
-#define DHD_PW(COT, TWO, RELU, EPI)                                                                                    \
-  do {                                                                                                                 \
-    if (g_gemm_mode >= 1) {                                                                                            \
-      if (grid.x > 0) {                                                                                                \
-        auto kern = pw_gemm6_kernel<COT, TWO, RELU, EPI>;                                                              \
-        DHD_LDS_ATTR_ONCE(kern, shmem);                                                                                \
-        hipLaunchKernelGGL(kern, grid, dim3(kPwBlock), shmem, st, in0, in1, in_bstride, in_bytes, coef,                \
-                           reinterpret_cast<const u32x4*>(wp), bias, relu_mask, stat_part, y, c, hw, 0, t_main, 0);    \
-      }                                                                                                                \
-      if (t_main < tps) {                                                                                              \
-        auto tail = pw_gemm6_kernel<4, TWO, RELU, EPI>;                                                                \
-        DHD_LDS_ATTR_ONCE(tail, shmem_tail);                                                                           \
-        hipLaunchKernelGGL(tail, grid_tail, dim3(kPwBlock), shmem_tail, st, in0, in1, in_bstride, in_bytes, coef,      \
-                           reinterpret_cast<const u32x4*>(wp), bias, relu_mask, stat_part, y, c, hw, t_main, tps, 1);  \
-      }                                                                                                                \
-    } else {                                                                                                           \
-      auto kern = pw_gemm_kernel<COT, TWO, RELU, EPI>;                                                                 \
-      DHD_LDS_ATTR_ONCE(kern, shmem);                    \
-      hipLaunchKernelGGL(kern, grid, dim3(kPwBlock), shmem, st, in0, in1, in_bstride, coef, wp, bias, aux, aux_scsh, y, \
-                         c, hw);                                                                                       \
-    }                                                                                                                  \
-  } while (0)
-#define DHD_PW_COT(TWO, RELU, EPI)           \
-  do {                                       \
-    if (cot == 4) DHD_PW(4, TWO, RELU, EPI); \
-    else DHD_PW(8, TWO, RELU, EPI);          \
-  } while (0)
-  if (epi == 0 && two && !relu) DHD_PW_COT(true, false, 0);
-  else if (epi == 0 && !two && relu) DHD_PW_COT(false, true, 0);
-  else if (epi == 1 && two && !relu) DHD_PW_COT(true, false, 1);
-  else if (epi == 2 && two && !relu) DHD_PW_COT(true, false, 2);
-  else return DHD_EUNSUPPORTED;
-#undef DHD_PW_COT
-#undef DHD_PW
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
+  return with_op(g.op, [&](auto v) {
+    using V = decltype(v);
+    auto run = [&](auto cot_c) {
+      constexpr int COT = decltype(cot_c)::value;
+      if (!six)
+        return launch_lds<pw_gemm_kernel<COT, V::two, V::relu, V::epi>>(grid, dim3(kPwBlock), shmem, shmem, st, g.in0, g.in1, g.in_bstride,
+                                                                        g.coef, static_cast<const float*>(g.wp), g.bias, g.aux, g.aux_scsh,
+                                                                        g.y, c, hw);
+      if (grid.x > 0) {
+        const int rc = launch_lds<pw_gemm6_kernel<COT, V::two, V::relu, V::epi>>(grid, dim3(kPwBlock), shmem, shmem, st, g.in0, g.in1,
+                                                                                 g.in_bstride, in_bytes, g.coef, wp, g.bias, g.mask,
+                                                                                 g.stat_part, g.y, c, hw, 0, t_main, 0);
+        if (rc != DHD_OK) return rc;
+      }
+      if (t_main < tps)
+        return launch_lds<pw_gemm6_kernel<4, V::two, V::relu, V::epi>>(grid_tail, dim3(kPwBlock), shmem_tail, shmem_tail, st, g.in0,
+                                                                       g.in1, g.in_bstride, in_bytes, g.coef, wp, g.bias, g.mask,
+                                                                       g.stat_part, g.y, c, hw, t_main, tps, 1);
+      return (int)DHD_OK;
+    };
+    return cot == 8 ? run(IntC<8>{}) : run(IntC<4>{});
+  });
 }
 
-int launch_pw_wgrad(const float* a0, const float* a1, const float* acoef, size_t a_bs, const float* b0, const float* b1,
-                    const float* bcoef, size_t b_bs, bool b_relu, float* partial, float* gw, int b, int c, int hw,
-                    hipStream_t st) {
-  // (tried at C = 256 in the bf16x3 mode: 128 x 128 tiles, two workgroups per CU, operands read twice through L2: 233 / 189 us
-  // against 166 / 138 us for one 256 x 256 tile per CU)
+template <class TS>
+int launch_gemm(const Plan& p, const GemmCall<TS>& g, int b, int c, int hw, hipStream_t st, int* stat_rows = nullptr) {
+  if constexpr (!std::is_same<TS, float>::value) {
+    return launch_gemm_cu(g, b, c, hw, st, stat_rows);   // Gemm::cuh
+  } else {
+    if (p.gemm == Gemm::cu) return launch_gemm_cu(g, b, c, hw, st, stat_rows);
+    if (p.gemm == Gemm::res) return launch_gemm_res(p, g, b, c, hw, st, stat_rows);
+    return launch_gemm_streamed(p, g, b, c, hw, st, stat_rows);
+  }
+}
+
+// Weight gradient gw = A . B^T over the pixels: A = BatchNorm-backward(a0, a1), B = the input of the GEMM `b_of` (conv1: blend1 of
+// b0 / b1, conv2: BatchNorm + ReLU of b0).  Per-worker partial matrices, reduced deterministically by wgrad_reduce_kernel.
+// (tried at C = 256 in the bf16x3 mode: 128 x 128 tiles, two workgroups per CU, operands read twice through L2: 233 / 189 us
+// against 166 / 138 us for one 256 x 256 tile per CU)
+template <class TS>
+int launch_wgrad(const Plan& p, Op b_of, const TS* a0, const TS* a1, const float* acoef, size_t a_bs, const TS* b0, const TS* b1,
+                 const float* bcoef, size_t b_bs, float* partial, float* gw, int b, int c, int hw, hipStream_t st) {
   const int ot = c == 128 ? 128 : 256;
   const int nob = (c / ot) * (c / ot);
   const int workers = kWgWorkers / nob > 0 ? kWgWorkers / nob : 1;
-  const dim3 grid(workers, nob);
-  const size_t shmem = (size_t)4 * ot * kWgStride * sizeof(float);
-#define DHD_WG(OT, ATWO, BTWO, BRELU)                                                                              \
-  do {                                                                                                             \
-    auto kern = pw_wgrad_kernel<OT, ATWO, BTWO, BRELU>;                                                            \
-    DHD_LDS_ATTR_ONCE(kern, shmem);                    \
-    hipLaunchKernelGGL(kern, grid, dim3(kWgBlock), shmem, st, a0, a1, acoef, a_bs, b0, b1, bcoef, b_bs, partial, c, \
-                       hw, b, workers);                                                                            \
-  } while (0)
-  const bool btwo = b1 != nullptr;
-  if (a1 == nullptr) return DHD_EUNSUPPORTED;
-  if (g_gemm_mode == 3) {
-    const size_t shmem3 = (size_t)2 * 2 * 2 * (ot / 32) * 2 * 64 * 16;
-#define DHD_WG3(OT, ATWO, BTWO, BRELU)                                                                             \
-  do {                                                                                                             \
-    auto kern = pw_wgrad3_kernel<OT, ATWO, BTWO, BRELU>;                                                           \
-    DHD_LDS_ATTR_ONCE(kern, shmem3);                                                                               \
-    hipLaunchKernelGGL(kern, grid, dim3(kWgBlock), shmem3, st, a0, a1, acoef, a_bs, b0, b1, bcoef, b_bs, partial,  \
-                       c, hw, b, workers);                                                                         \
-  } while (0)
-    if (ot == 128) {
-      if (btwo) DHD_WG3(128, true, true, false);
-      else if (b_relu) DHD_WG3(128, true, false, true);
-      else return DHD_EUNSUPPORTED;
-    } else {
-      if (btwo) DHD_WG3(256, true, true, false);
-      else if (b_relu) DHD_WG3(256, true, false, true);
-      else return DHD_EUNSUPPORTED;
-    }
-#undef DHD_WG3
-  } else if (g_gemm_mode >= 1) {
-    const size_t shmem6 = (size_t)2 * 2 * (ot / 32) * 3 * 64 * 16;
-#define DHD_WG6(OT, ATWO, BTWO, BRELU)                                                                             \
-  do {                                                                                                             \
-    auto kern = pw_wgrad6_kernel<OT, ATWO, BTWO, BRELU>;                                                           \
-    DHD_LDS_ATTR_ONCE(kern, shmem6);                    \
-    hipLaunchKernelGGL(kern, grid, dim3(kWgBlock), shmem6, st, a0, a1, acoef, a_bs, b0, b1, bcoef, b_bs, partial,  \
-                       c, hw, b, workers);                                                                         \
-  } while (0)
-    if (ot == 128) {
-      if (btwo) DHD_WG6(128, true, true, false);
-      else if (b_relu) DHD_WG6(128, true, false, true);
-      else return DHD_EUNSUPPORTED;
-    } else {
-      if (btwo) DHD_WG6(256, true, true, false);
-      else if (b_relu) DHD_WG6(256, true, false, true);
-      else return DHD_EUNSUPPORTED;
-    }
-#undef DHD_WG6
-  } else if (ot == 128) {
-    if (btwo) DHD_WG(128, true, true, false);
-    else if (b_relu) DHD_WG(128, true, false, true);
-    else return DHD_EUNSUPPORTED;
-  } else {
-    if (btwo) DHD_WG(256, true, true, false);
-    else if (b_relu) DHD_WG(256, true, false, true);
-    else return DHD_EUNSUPPORTED;
-  }
-#undef DHD_WG
-  DHD_LAUNCH_CHECK();
+  const dim3 grid(workers, nob), block(kWgBlock);
+  const int rc = with_op(b_of, [&](auto v) {
+    using V = decltype(v);
+    auto run = [&](auto ot_c) {
+      constexpr int OT = decltype(ot_c)::value;
+      if constexpr (!std::is_same<TS, float>::value) {
+        const size_t shmem = (size_t)2 * 4 * 2 * (OT / 32) * 64 * 16;
+        return launch_lds<pw_wgrad_h_kernel<TS, OT, V::two, V::relu>>(grid, block, shmem, shmem, st, a0, a1, acoef, a_bs, b0, b1, bcoef,
+                                                                     b_bs, partial, c, hw, b, workers);
+      } else if (p.wgrad == Wgrad::w3) {
+        const size_t shmem = (size_t)2 * 2 * 2 * (OT / 32) * 2 * 64 * 16;
+        return launch_lds<pw_wgrad3_kernel<OT, true, V::two, V::relu>>(grid, block, shmem, shmem, st, a0, a1, acoef, a_bs, b0, b1, bcoef,
+                                                                      b_bs, partial, c, hw, b, workers);
+      } else if (p.wgrad == Wgrad::w6) {
+        const size_t shmem = (size_t)2 * 2 * (OT / 32) * 3 * 64 * 16;
+        return launch_lds<pw_wgrad6_kernel<OT, true, V::two, V::relu>>(grid, block, shmem, shmem, st, a0, a1, acoef, a_bs, b0, b1, bcoef,
+                                                                      b_bs, partial, c, hw, b, workers);
+      } else {
+        const size_t shmem = (size_t)4 * OT * kWgStride * sizeof(float);
+        return launch_lds<pw_wgrad_kernel<OT, true, V::two, V::relu>>(grid, block, shmem, shmem, st, a0, a1, acoef, a_bs, b0, b1, bcoef,
+                                                                     b_bs, partial, c, hw, b, workers);
+      }
+    };
+    return ot == 128 ? run(IntC<128>{}) : run(IntC<256>{});
+  });
+  if (rc != DHD_OK) return rc;
   const int n = c * c;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(dhd_cdiv(n, DHD_WAVE)), dim3(kEwBlock), 0, st, partial, gw, n, workers);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
 
-#include "sfa_stage_half.h"
+// The channel means of x and the four weight images of a call: conv1 and conv2 (scratch), their transposes for the data
+// gradients (saved).  dst: conv1, conv2, conv1^T, conv2^T.
+int launch_mean_pack(const Plan& p, const float* x, const float* w1, const float* w2, void* const dst[4], float* mean_part, int b,
+                     int c, int hw, hipStream_t st) {
+  const int blocks_each = dhd_cdiv((c / 32) * (c / 16) * 64, kEwBlock);
+  if (p.pack == Pack::cu || p.pack == Pack::res) {   // one launch: the images in rows of extra blocks
+    PackJob job;
+    job.w[0] = w1; job.w[1] = w2;
+    for (int i = 0; i < 4; ++i) job.dst[i] = static_cast<u32x4*>(dst[i]);
+    job.c = c; job.nt = p.nt; job.cob = p.cob; job.cu = p.pack == Pack::cu ? 1 : 0;
+    job.blocks_each = blocks_each;
+    const dim3 grid(kPlaneChunks, b * 2 * c + dhd_cdiv(4 * blocks_each, kPlaneChunks));
+    hipLaunchKernelGGL(plane_mean_pack_kernel, grid, dim3(kEwBlock), 0, st, x, mean_part, hw, b * 2 * c, job);
+    DHD_LAUNCH_CHECK();
+    return DHD_OK;
+  }
+  hipLaunchKernelGGL(plane_mean_kernel, dim3(kPlaneChunks, b * 2 * c), dim3(kEwBlock), 0, st, x, mean_part, hw);
+  DHD_LAUNCH_CHECK();
+  for (int i = 0; i < 4; ++i) {   // the streamed / f32 forms pack one weight per launch
+    const float* wi = i & 1 ? w2 : w1;
+    if (p.pack == Pack::six)
+      hipLaunchKernelGGL(pack_weight6_kernel, dim3(blocks_each), dim3(kEwBlock), 0, st, wi, i >> 1, static_cast<u32x4*>(dst[i]), c, p.cot);
+    else
+      hipLaunchKernelGGL(pack_weight_kernel, dim3(dhd_cdiv(c * c, kEwBlock)), dim3(kEwBlock), 0, st, wi, i >> 1, static_cast<float*>(dst[i]),
+                         c, p.cot);
+    DHD_LAUNCH_CHECK();
+  }
+  return DHD_OK;
+}
+template <class TS>
+int launch_mean_pack(const Plan&, const TS* x, const float* w1, const float* w2, void* const dst[4], float* mean_part, int b, int c,
+                     int hw, hipStream_t st) {
+  PackJobH job;
+  job.w[0] = w1; job.w[1] = w2;
+  for (int i = 0; i < 4; ++i) job.dst[i] = static_cast<u32x4*>(dst[i]);
+  job.c = c;
+  job.blocks_each = dhd_cdiv((c / 32) * (c / 16) * 64, kEwBlock);
+  const dim3 grid(kPlaneChunks, b * 2 * c + dhd_cdiv(4 * job.blocks_each, kPlaneChunks));
+  hipLaunchKernelGGL(plane_mean_pack_h_kernel<TS>, grid, dim3(kEwBlock), 0, st, x, mean_part, hw, b * 2 * c, job);
+  DHD_LAUNCH_CHECK();
+  return DHD_OK;
+}
 
-// dhd_sfa_weights.storage_dtype of a call: DHD_F32, or the half type every tensor of the stage is stored in (== io_dtype)
-inline int storage_of(const dhd_sfa_weights* w, int c, int hw, int* storage) {
-  *storage = w->storage_dtype;
-  if (*storage == DHD_F32) return DHD_OK;
-  if (*storage != DHD_F16 && *storage != DHD_BF16) return DHD_EINVAL;
-  if (w->io_dtype != *storage) return DHD_EINVAL;
-  return half_storage_supported(c, hw) ? DHD_OK : DHD_EUNSUPPORTED;
+// The element-wise kernels that read or write tensors of the storage type TS, or the I/O tensors (out, gout, gx) of type TO:
+// half storage (TO == TS) ...
+template <class TS, class TO>
+struct Ew {
+  static_assert(std::is_same<TS, TO>::value, "half storage: the I/O tensors are of the storage type");
+  static constexpr auto blend2 = blend2_bn_h_kernel<TS>;
+  static constexpr auto blend2_bwd = blend2_bn_bwd_h_kernel<TS>;
+  static constexpr auto pair_sums = pair_sums_h_kernel<TS>;
+  static constexpr auto blend1_da = blend1_da_h_kernel<TS>;
+  static constexpr auto gx = stage_gx_h_kernel<TS>;
+};
+// ... and float32 storage with float32 or half I/O (dhd_sfa_weights.io_dtype)
+template <class TO>
+struct Ew<float, TO> {
+  static constexpr auto blend2 = blend2_bn_kernel<TO>;
+  static constexpr auto blend2_bwd = blend2_bn_bwd_kernel<TO>;
+  static constexpr auto pair_sums = pair_sums_kernel;
+  static constexpr auto blend1_da = blend1_da_kernel;
+  static constexpr auto gx = stage_gx_kernel<TO>;
+};
+
+// Forward in up to three phases, cut at the two BatchNorm statistics points.  sync == nullptr: all phases in one call with
+// this call's own statistics.  sync != nullptr (nn.SyncBatchNorm): phases [lo, hi]; a phase that ends at a statistics point
+// leaves this rank's sums in `sync` ((2C + 1) doubles: [sum (y - bias)][C] | [sum (y - bias)^2][C] | count), the next phase
+// starts from the caller's all-reduced vector in the same place.
+template <class TS, class TO>
+int stage_forward(const Plan& p, const TS* x, const dhd_sfa_weights* w, TO* out, void* saved, void* scratch, int b, int c, int hw,
+                  int lo, int hi, double* sync, hipStream_t st) {
+  const int r = w->hidden;
+  const SavedLayout S = saved_layout(b, c, hw, r, p.storage);
+  const ScratchLayout T = scratch_layout(b, c, hw, r, p.storage);
+  char* sv = static_cast<char*>(saved);
+  char* sc = static_cast<char*>(scratch);
+  auto SF = [&](size_t off) { return reinterpret_cast<float*>(sv + off); };
+  auto TF = [&](size_t off) { return reinterpret_cast<float*>(sc + off); };
+  TS* y1 = reinterpret_cast<TS*>(sv + S.y1);
+  TS* y2 = reinterpret_cast<TS*>(sv + S.y2);
+  float* stat_part = p.fused_stats ? TF(T.stat_part) : nullptr;
+  const dim3 planes(kPlaneChunks, b * c), per_ch(dhd_cdiv(c, kEwBlock));
+  const size_t cs = (size_t)c * hw;
+  int stat_rows = 0, rc;
+  struct Bn {
+    const float *shift, *gamma, *beta;
+    float *run_mean, *run_var;
+    float momentum, eps;
+    long long* batches;
+    float *mean, *rstd, *scsh;
+    double* loc;
+  };
+  const Bn bn1 = {w->conv1_b, w->bn1_w, w->bn1_b, w->bn1_mean, w->bn1_var, w->momentum1, w->eps1,
+                  reinterpret_cast<long long*>(w->bn1_batches), SF(S.mean1), SF(S.rstd1), SF(S.scsh1), reinterpret_cast<double*>(sv + S.loc1)};
+  const Bn bn2 = {w->conv2_b, w->bn2_w, w->bn2_b, w->bn2_mean, w->bn2_var, w->momentum2, w->eps2,
+                  reinterpret_cast<long long*>(w->bn2_batches), SF(S.mean2), SF(S.rstd2), SF(S.scsh2), reinterpret_cast<double*>(sv + S.loc2)};
+  // a phase that ends at a statistics point: this rank's sums only (also kept in `saved` for the backward's bias gradient)
+  auto publish = [&](const Bn& n, float* tab) {
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, TF(T.stat_part), stat_rows, n.shift, n.gamma, n.beta,
+                       n.run_mean, n.run_var, n.momentum, n.eps, n.mean, n.rstd, n.scsh, tab, b, c, hw, sync, n.loc, nullptr, nullptr);
+  };
+  // the layer's coefficient tables: batch statistics (training) or the running ones
+  auto coef = [&](const Bn& n, const TS* y, float* tab) {
+    if (!w->training) {
+      hipLaunchKernelGGL(bn_eval_coef_kernel, per_ch, dim3(kEwBlock), 0, st, n.gamma, n.beta, n.run_mean, n.run_var, n.eps, n.mean, n.rstd,
+                         n.scsh, tab, b, c);
+    } else if (p.fused_stats) {   // the GEMM epilogue left per-(sample, wave tile) sums shifted by the bias
+      hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, TF(T.stat_part), stat_rows, n.shift, n.gamma, n.beta,
+                         n.run_mean, n.run_var, n.momentum, n.eps, n.mean, n.rstd, n.scsh, tab, b, c, hw, nullptr, nullptr, sync, n.batches);
+    } else if constexpr (std::is_same<TS, float>::value) {   // f32 GEMMs: a statistics pass of their own
+      hipLaunchKernelGGL(moments_kernel, planes, dim3(kEwBlock), 0, st, y, TF(T.part), c, hw);
+      hipLaunchKernelGGL(bn_train_finalize_kernel, per_ch, dim3(kEwBlock), 0, st, TF(T.part), b * kPlaneChunks, y, hw, n.gamma, n.beta,
+                         n.run_mean, n.run_var, n.momentum, n.eps, n.mean, n.rstd, n.scsh, tab, b, c, hw, n.batches);
+    }
+  };
+  if (sync && !p.fused_stats) return DHD_EUNSUPPORTED;   // cross-rank statistics: training mode, bf16 GEMM precisions or half storage
+
+  if (lo <= 0) {
+    void* const dst[4] = {sc + T.wp1, sc + T.wp2, sv + S.wp1t, sv + S.wp2t};
+    rc = launch_mean_pack(p, x, w->conv1_w, w->conv2_w, dst, TF(T.mean_part), b, c, hw, st);
+    if (rc != DHD_OK) return rc;
+    hipLaunchKernelGGL(fc_forward_kernel, dim3(b), dim3(kFcBlock), (size_t)(2 * c + r) * sizeof(float), st, TF(T.mean_part), w->fc1_w,
+                       w->fc1_b, w->fc2_w, w->fc2_b, SF(S.s), SF(S.h), SF(S.a1), SF(S.tab_a), c, r, hw, reinterpret_cast<int*>(sv + S.tick),
+                       2 * c + kTickWords);
+    DHD_LAUNCH_CHECK();
+    // y1 = conv1(blend1(x))
+    rc = launch_gemm(p, GemmCall<TS>{kConv1, x, x + cs, 2 * cs, c, SF(S.tab_a), sc + T.wp1, w->conv1_b, nullptr, stat_part, y1},
+                     b, c, hw, st, &stat_rows);
+    if (rc != DHD_OK) return rc;
+    if (sync) {
+      publish(bn1, SF(S.tab1));
+      DHD_LAUNCH_CHECK();
+    }
+  }
+  if (hi <= 0) return DHD_OK;
+  if (lo <= 1) {
+    coef(bn1, y1, SF(S.tab1));
+    DHD_LAUNCH_CHECK();
+    // y2 = conv2(relu(bn1(y1)))
+    rc = launch_gemm(p, GemmCall<TS>{kConv2, y1, nullptr, cs, c, SF(S.tab1), sc + T.wp2, w->conv2_b,
+                                     reinterpret_cast<unsigned*>(sv + S.mask), stat_part, y2},
+                     b, c, hw, st, &stat_rows);
+    if (rc != DHD_OK) return rc;
+    if (sync) {
+      publish(bn2, TF(T.tab_g2));
+      DHD_LAUNCH_CHECK();
+    }
+  }
+  if (hi <= 1) return DHD_OK;
+  coef(bn2, y2, TF(T.tab_g2));   // bn2 has no consumer GEMM in the forward: the table slot is a sink
+  using E = Ew<TS, TO>;
+  hipLaunchKernelGGL(E::blend2, planes, dim3(kEwBlock), 0, st, x, SF(S.a1), y2, SF(S.scsh2), out, c, hw);
+  DHD_LAUNCH_CHECK();
+  return DHD_OK;
+}
+
+// Backward in up to three phases, cut where the two BatchNorm backward passes need their sums (sum g, sum g (y - mu)); `sync`
+// as in stage_forward ((2C + 1) doubles: [sum g][C] | [sum g (y - mu)][C] | count).
+template <class TS, class TO>
+int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const void* saved, const TO* gout, TO* gx,
+                   const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw, int lo, int hi, double* sync, hipStream_t st) {
+  using E = Ew<TS, TO>;
+  const int r = w->hidden;
+  const SavedLayout S = saved_layout(b, c, hw, r, p.storage);
+  const ScratchLayout T = scratch_layout(b, c, hw, r, p.storage);
+  char* sv = const_cast<char*>(static_cast<const char*>(saved));
+  char* sc = static_cast<char*>(scratch);
+  auto SF = [&](size_t off) { return reinterpret_cast<float*>(sv + off); };
+  auto TF = [&](size_t off) { return reinterpret_cast<float*>(sc + off); };
+  const TS* y1 = reinterpret_cast<const TS*>(sv + S.y1);
+  const TS* y2 = reinterpret_cast<const TS*>(sv + S.y2);
+  TS* g2 = reinterpret_cast<TS*>(sc + T.g2);
+  TS* g1 = reinterpret_cast<TS*>(sc + T.g1);
+  TS* du = reinterpret_cast<TS*>(sc + T.du);
+  unsigned* mask = reinterpret_cast<unsigned*>(sv + S.mask);
+  int* tick = reinterpret_cast<int*>(sv + S.tick);
+  const dim3 planes(kPlaneChunks, b * c), per_ch(dhd_cdiv(c, kEwBlock));
+  const size_t cs = (size_t)c * hw;
+  int rc;
+  // without cross-rank statistics the pass that makes a layer's sums finishes its own reduction (BnTail, on that layer's
+  // arrival counters): no bn_backward_coef launch
+  const BnTail tail2 = {sync ? nullptr : tick, w->bn2_w, SF(S.mean2), SF(S.rstd2), TF(T.tab_g2), grads->bn2_w, grads->bn2_b,
+                        grads->conv2_b, w->training, b, hw};
+  const BnTail tail1 = {sync ? nullptr : tick + c, w->bn1_w, SF(S.mean1), SF(S.rstd1), TF(T.tab_g1), grads->bn1_w, grads->bn1_b,
+                        grads->conv1_b, w->training, b, hw};
+  // with them: this rank's sums out at the end of a phase, the all-reduced ones in at the start of the next
+  auto coef_out = [&](const BnTail& t) {
+    hipLaunchKernelGGL(bn_backward_coef_kernel, per_ch, dim3(kEwBlock), 0, st, TF(T.part), t.gamma, t.mean, t.rstd, w->training, t.tab,
+                       t.dgamma, t.dbeta, t.dbias, b, c, hw, sync, nullptr, nullptr, nullptr);
+  };
+  auto coef_in = [&](const BnTail& t, size_t loc, const float* bias) {
+    hipLaunchKernelGGL(bn_backward_coef_kernel, per_ch, dim3(kEwBlock), 0, st, TF(T.part), t.gamma, t.mean, t.rstd, w->training, t.tab,
+                       t.dgamma, t.dbeta, t.dbias, b, c, hw, nullptr, sync, reinterpret_cast<const double*>(sv + loc), bias);
+  };
+  if (sync && !p.fused_stats) return DHD_EUNSUPPORTED;
+
+  if (lo <= 0) {
+    // g2 = dL/ds2, BatchNorm-2 sums, go-part of dL/da
+    hipLaunchKernelGGL(E::blend2_bwd, planes, dim3(kEwBlock), 0, st, x, SF(S.a1), y2, SF(S.scsh2), SF(S.mean2), gout, g2, TF(T.part),
+                       TF(T.da1), c, hw, tail2);
+    if (sync) coef_out(tail2);
+    DHD_LAUNCH_CHECK();
+  }
+  if (hi <= 0) return DHD_OK;
+  if (lo <= 1) {
+    if (sync) coef_in(tail2, S.loc2, w->conv2_b);
+    DHD_LAUNCH_CHECK();
+    // dW2 = dy2 . z1^T
+    rc = launch_wgrad<TS>(p, kConv2, g2, y2, TF(T.tab_g2), cs, y1, nullptr, SF(S.tab1), cs, TF(T.wpart), grads->conv2_w, b, c, hw, st);
+    if (rc != DHD_OK) return rc;
+    // g1 = (W2^T dy2) * [z1 > 0]
+    rc = launch_gemm(p, GemmCall<TS>{kDgrad2, g2, y2, cs, c, TF(T.tab_g2), sv + S.wp2t, nullptr, mask, nullptr, g1, y1, SF(S.scsh1)},
+                     b, c, hw, st);
+    if (rc != DHD_OK) return rc;
+    hipLaunchKernelGGL(E::pair_sums, planes, dim3(kEwBlock), 0, st, g1, y1, SF(S.mean1), TF(T.part), c, hw, tail1);
+    if (sync) coef_out(tail1);
+    DHD_LAUNCH_CHECK();
+  }
+  if (hi <= 1) return DHD_OK;
+  if (sync) coef_in(tail1, S.loc1, w->conv1_b);
+  DHD_LAUNCH_CHECK();
+  // dW1 = dy1 . u^T
+  rc = launch_wgrad<TS>(p, kConv1, g1, y1, TF(T.tab_g1), cs, x, x + cs, SF(S.tab_a), 2 * cs, TF(T.wpart), grads->conv1_w, b, c, hw, st);
+  if (rc != DHD_OK) return rc;
+  // du = W1^T dy1
+  rc = launch_gemm(p, GemmCall<TS>{kDgrad1, g1, y1, cs, c, TF(T.tab_g1), sv + S.wp1t, nullptr, nullptr, nullptr, du}, b, c, hw, st);
+  if (rc != DHD_OK) return rc;
+  hipLaunchKernelGGL(E::blend1_da, planes, dim3(kEwBlock), 0, st, x, du, TF(T.da2), c, hw);
+  hipLaunchKernelGGL(fc_backward_kernel, dim3(b), dim3(kEwBlock), (size_t)(c + r + kEwBlock) * sizeof(float), st, TF(T.da1), TF(T.da2),
+                     SF(S.a1), SF(S.h), w->fc1_w, w->fc2_w, TF(T.dpre2), TF(T.dh), TF(T.ds), c, r);
+  const int n_fc = r * 2 * c + c * r + r + c;
+  const FcGradJob fcj = {TF(T.dpre2), TF(T.dh), SF(S.h), SF(S.s), grads->fc1_w, grads->fc1_b, grads->fc2_w, grads->fc2_b, b, r};
+  const int fc_rows = dhd_cdiv(dhd_cdiv(n_fc, kEwBlock), kPlaneChunks);
+  const dim3 planes_fc(kPlaneChunks, b * c + fc_rows);
+  hipLaunchKernelGGL(E::gx, planes_fc, dim3(kEwBlock), 0, st, SF(S.a1), y2, SF(S.scsh2), gout, du, TF(T.ds), gx, c, hw, fc_rows, fcj);
+  DHD_LAUNCH_CHECK();
+  return DHD_OK;
+}
+
+// The driver instance of a call: storage type, and on float32 storage the I/O type
+template <class F>
+int with_types(const Plan& p, int io_dtype, F&& f) {
+  if (p.storage == DHD_F16) return f((_Float16*)nullptr, (_Float16*)nullptr);
+  if (p.storage == DHD_BF16) return f((__bf16*)nullptr, (__bf16*)nullptr);
+  if (io_dtype == DHD_F16) return f((float*)nullptr, (_Float16*)nullptr);
+  if (io_dtype == DHD_BF16) return f((float*)nullptr, (__bf16*)nullptr);
+  return f((float*)nullptr, (float*)nullptr);
+}
+
+static int stage_forward_entry(const void* x, const dhd_sfa_weights* w, void* out, void* saved, void* scratch, int b, int c, int hw,
+                               int lo, int hi, double* sync, void* stream) {
+  if (!x || !w || !saved || !scratch || b <= 0 || (hi == 2 && !out)) return DHD_EINVAL;
+  if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
+  if (!w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b || !w->conv1_w || !w->conv1_b || !w->bn1_w || !w->bn1_b || !w->conv2_w ||
+      !w->conv2_b || !w->bn2_w || !w->bn2_b)
+    return DHD_EINVAL;
+  if (!w->training && (!w->bn1_mean || !w->bn1_var || !w->bn2_mean || !w->bn2_var)) return DHD_EINVAL;
+  Plan p;
+  if (int rc = make_plan(w, c, hw, &p); rc != DHD_OK) return rc;
+  return with_types(p, w->io_dtype, [&](auto* ts, auto* to) {
+    using TS = std::remove_pointer_t<decltype(ts)>;
+    using TO = std::remove_pointer_t<decltype(to)>;
+    return stage_forward<TS, TO>(p, static_cast<const TS*>(x), w, static_cast<TO*>(out), saved, scratch, b, c, hw, lo, hi, sync,
+                                 dhd_stream(stream));
+  });
+}
+
+static int stage_backward_entry(const void* x, const dhd_sfa_weights* w, const void* saved, const void* gout, void* gx,
+                                const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw, int lo, int hi, double* sync,
+                                void* stream) {
+  if (!x || !w || !saved || !gout || !grads || !scratch || b <= 0 || (hi == 2 && !gx)) return DHD_EINVAL;
+  if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
+  if (!grads->fc1_w || !grads->fc1_b || !grads->fc2_w || !grads->fc2_b || !grads->conv1_w || !grads->conv1_b || !grads->bn1_w ||
+      !grads->bn1_b || !grads->conv2_w || !grads->conv2_b || !grads->bn2_w || !grads->bn2_b)
+    return DHD_EINVAL;
+  Plan p;
+  if (int rc = make_plan(w, c, hw, &p); rc != DHD_OK) return rc;
+  return with_types(p, w->io_dtype, [&](auto* ts, auto* to) {
+    using TS = std::remove_pointer_t<decltype(ts)>;
+    using TO = std::remove_pointer_t<decltype(to)>;
+    return stage_backward<TS, TO>(p, static_cast<const TS*>(x), w, saved, static_cast<const TO*>(gout), static_cast<TO*>(gx), grads,
+                                  scratch, b, c, hw, lo, hi, sync, dhd_stream(stream));
+  });
 }
 
 }  // namespace
@@ -1442,12 +1710,12 @@ int dhd_sfa_stage_supported(int c, int hw) { return stage_supported(c, hw) ? 1 :
 
 size_t dhd_sfa_stage_saved_bytes(int b, int c, int hw, int hidden) {
   if (b <= 0 || hidden <= 0 || !stage_supported(c, hw)) return 0;
-  return saved_layout(b, c, hw, hidden).total * sizeof(float);
+  return saved_layout(b, c, hw, hidden, DHD_F32).total;
 }
 
 size_t dhd_sfa_stage_scratch_bytes(int b, int c, int hw, int hidden) {
   if (b <= 0 || hidden <= 0 || !stage_supported(c, hw)) return 0;
-  return scratch_layout(b, c, hw, hidden).total * sizeof(float);
+  return scratch_layout(b, c, hw, hidden, DHD_F32).total;
 }
 
 int dhd_sfa_stage_half_storage_supported(int c, int hw) { return half_storage_supported(c, hw) ? 1 : 0; }
@@ -1456,263 +1724,36 @@ int dhd_sfa_stage_workspace_bytes(int b, int c, int hw, int hidden, int storage_
   if (b <= 0 || hidden <= 0 || !saved_bytes || !scratch_bytes) return DHD_EINVAL;
   if (storage_dtype == DHD_F32) {
     if (!stage_supported(c, hw)) return DHD_EUNSUPPORTED;
-    *saved_bytes = saved_layout(b, c, hw, hidden).total * sizeof(float);
-    *scratch_bytes = scratch_layout(b, c, hw, hidden).total * sizeof(float);
-    return DHD_OK;
-  }
-  if (storage_dtype != DHD_F16 && storage_dtype != DHD_BF16) return DHD_EINVAL;
-  if (!half_storage_supported(c, hw)) return DHD_EUNSUPPORTED;
-  *saved_bytes = saved_layout_h(b, c, hw, hidden).total;
-  *scratch_bytes = scratch_layout_h(b, c, hw, hidden).total;
-  return DHD_OK;
-}
-
-// Forward in up to three phases, cut at the two BatchNorm statistics points.  sync == nullptr: all phases in one call with
-// this call's own statistics.  sync != nullptr (nn.SyncBatchNorm): phases [lo, hi]; a phase that ends at a statistics point
-// leaves this rank's sums in `sync` ((2C + 1) doubles: [sum (y - bias)][C] | [sum (y - bias)^2][C] | count), the next phase
-// starts from the caller's all-reduced vector in the same place.
-static int stage_forward_impl(const void* xv, const dhd_sfa_weights* w, void* out, void* saved, void* scratch, int b, int c, int hw,
-                              int lo, int hi, double* sync, void* stream) {
-  if (!xv || !w || !saved || !scratch || b <= 0 || (hi == 2 && !out)) return DHD_EINVAL;
-  if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
-  if (!w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b || !w->conv1_w || !w->conv1_b || !w->bn1_w || !w->bn1_b || !w->conv2_w ||
-      !w->conv2_b || !w->bn2_w || !w->bn2_b)
-    return DHD_EINVAL;
-  if (!w->training && (!w->bn1_mean || !w->bn1_var || !w->bn2_mean || !w->bn2_var)) return DHD_EINVAL;
-  if (set_call_mode(w->gemm) != DHD_OK) return DHD_EINVAL;
-  if (w->io_dtype != DHD_F32 && w->io_dtype != DHD_F16 && w->io_dtype != DHD_BF16) return DHD_EINVAL;
-  hipStream_t st = dhd_stream(stream);
-  int storage;
-  if (int rcs = storage_of(w, c, hw, &storage); rcs != DHD_OK) return rcs;
-  if (storage == DHD_F16) return stage_forward_half<_Float16>(xv, w, out, saved, scratch, b, c, hw, lo, hi, sync, st);
-  if (storage == DHD_BF16) return stage_forward_half<__bf16>(xv, w, out, saved, scratch, b, c, hw, lo, hi, sync, st);
-  const float* x = static_cast<const float*>(xv);
-  const int r = w->hidden;
-  const SavedLayout S = saved_layout(b, c, hw, r);
-  const ScratchLayout T = scratch_layout(b, c, hw, r);
-  float* sv = static_cast<float*>(saved);
-  float* sc = static_cast<float*>(scratch);
-  const dim3 planes2(kPlaneChunks, b * 2 * c), planes(kPlaneChunks, b * c);
-  const dim3 per_ch(dhd_cdiv(c, kEwBlock));
-  const bool fused_stats = w->training && g_gemm_mode >= 1;  // BatchNorm sums come out of the GEMM epilogue
-  if (sync && !fused_stats) return DHD_EUNSUPPORTED;         // cross-rank statistics: training mode, bf16 GEMM precisions
-  int stat_rows = 0;
-  int rc;
-
-  if (lo <= 0) {
-    if (res_supported(c)) {
-      PackJob job;
-      job.w[0] = w->conv1_w; job.w[1] = w->conv2_w;
-      job.dst[0] = reinterpret_cast<u32x4*>(sc + T.wp1); job.dst[1] = reinterpret_cast<u32x4*>(sc + T.wp2);
-      job.dst[2] = reinterpret_cast<u32x4*>(sv + S.wp1t); job.dst[3] = reinterpret_cast<u32x4*>(sv + S.wp2t);
-      job.c = c; job.nt = mode_terms(); job.cob = res_cob(c, job.nt); job.cu = cu_supported(c) ? 1 : 0;
-      job.blocks_each = dhd_cdiv((c / 32) * (c / 16) * 64, kEwBlock);
-      const dim3 grid(kPlaneChunks, b * 2 * c + dhd_cdiv(4 * job.blocks_each, kPlaneChunks));
-      hipLaunchKernelGGL(plane_mean_pack_kernel, grid, dim3(kEwBlock), 0, st, x, sc + T.mean_part, hw, b * 2 * c, job);
-    } else {
-      hipLaunchKernelGGL(plane_mean_kernel, planes2, dim3(kEwBlock), 0, st, x, sc + T.mean_part, hw);
-      rc = launch_pack(w->conv1_w, 0, sc + T.wp1, c, st, w->conv2_w, sc + T.wp2);
-      if (rc != DHD_OK) return rc;
-      rc = launch_pack(w->conv1_w, 1, sv + S.wp1t, c, st, w->conv2_w, sv + S.wp2t);
-      if (rc != DHD_OK) return rc;
-    }
-    hipLaunchKernelGGL(fc_forward_kernel, dim3(b), dim3(kFcBlock), (size_t)(2 * c + r) * sizeof(float), st, sc + T.mean_part,
-                       w->fc1_w, w->fc1_b, w->fc2_w, w->fc2_b, sv + S.s, sv + S.h, sv + S.a1, sv + S.tab_a, c, r, hw,
-                       reinterpret_cast<int*>(sv + S.tick), 2 * c + kTickWords);
-    DHD_LAUNCH_CHECK();
-    // y1 = conv1(blend1(x))
-    rc = launch_pw_gemm(x, x + (size_t)c * hw, (size_t)2 * c * hw, c, sv + S.tab_a, false, sc + T.wp1, w->conv1_b, nullptr, nullptr,
-                        nullptr, fused_stats ? sc + T.stat_part : nullptr, sv + S.y1, 0, b, c, hw, st, &stat_rows);
-    if (rc != DHD_OK) return rc;
-    if (sync) {   // this rank's sums only (also kept in `saved` for the backward's convolution-bias gradient)
-      hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, sc + T.stat_part, stat_rows, w->conv1_b, w->bn1_w,
-                         w->bn1_b, w->bn1_mean, w->bn1_var, w->momentum1, w->eps1, sv + S.mean1, sv + S.rstd1, sv + S.scsh1,
-                         sv + S.tab1, b, c, hw, sync, reinterpret_cast<double*>(sv + S.loc1), nullptr, nullptr);
-      DHD_LAUNCH_CHECK();
-    }
-  }
-  if (hi <= 0) return DHD_OK;
-  if (lo <= 1) {
-    if (w->training) {
-      if (fused_stats) {  // the GEMM epilogue left per-(sample, wave tile) sums shifted by the bias
-        hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, sc + T.stat_part, stat_rows, w->conv1_b, w->bn1_w,
-                           w->bn1_b, w->bn1_mean, w->bn1_var, w->momentum1, w->eps1, sv + S.mean1, sv + S.rstd1, sv + S.scsh1,
-                           sv + S.tab1, b, c, hw, nullptr, nullptr, sync, reinterpret_cast<long long*>(w->bn1_batches));
-      } else {
-        hipLaunchKernelGGL(moments_kernel, planes, dim3(kEwBlock), 0, st, sv + S.y1, sc + T.part, c, hw);
-        hipLaunchKernelGGL(bn_train_finalize_kernel, per_ch, dim3(kEwBlock), 0, st, sc + T.part, b * kPlaneChunks, sv + S.y1, hw, w->bn1_w,
-                           w->bn1_b, w->bn1_mean, w->bn1_var, w->momentum1, w->eps1, sv + S.mean1, sv + S.rstd1, sv + S.scsh1,
-                           sv + S.tab1, b, c, hw, reinterpret_cast<long long*>(w->bn1_batches));
-      }
-    } else {
-      hipLaunchKernelGGL(bn_eval_coef_kernel, per_ch, dim3(kEwBlock), 0, st, w->bn1_w, w->bn1_b, w->bn1_mean, w->bn1_var, w->eps1,
-                         sv + S.mean1, sv + S.rstd1, sv + S.scsh1, sv + S.tab1, b, c);
-    }
-    DHD_LAUNCH_CHECK();
-    // y2 = conv2(relu(bn1(y1)))
-    rc = launch_pw_gemm(sv + S.y1, nullptr, (size_t)c * hw, c, sv + S.tab1, true, sc + T.wp2, w->conv2_b, nullptr, nullptr,
-                        reinterpret_cast<unsigned*>(sv + S.mask), fused_stats ? sc + T.stat_part : nullptr, sv + S.y2, 0,
-                        b, c, hw, st, &stat_rows);
-    if (rc != DHD_OK) return rc;
-    if (sync) {
-      hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, sc + T.stat_part, stat_rows, w->conv2_b, w->bn2_w,
-                         w->bn2_b, w->bn2_mean, w->bn2_var, w->momentum2, w->eps2, sv + S.mean2, sv + S.rstd2, sv + S.scsh2,
-                         sc + T.tab_g2, b, c, hw, sync, reinterpret_cast<double*>(sv + S.loc2), nullptr, nullptr);
-      DHD_LAUNCH_CHECK();
-    }
-  }
-  if (hi <= 1) return DHD_OK;
-  float* tab_unused = sc + T.tab_g2;  // bn2 has no consumer GEMM in forward; table slot reused as a sink
-  if (w->training) {
-    if (fused_stats) {  // the GEMM epilogue left per-(sample, wave tile) sums shifted by the bias
-      hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, sc + T.stat_part, stat_rows, w->conv2_b, w->bn2_w,
-                         w->bn2_b, w->bn2_mean, w->bn2_var, w->momentum2, w->eps2, sv + S.mean2, sv + S.rstd2, sv + S.scsh2,
-                         tab_unused, b, c, hw, nullptr, nullptr, sync, reinterpret_cast<long long*>(w->bn2_batches));
-    } else {
-      hipLaunchKernelGGL(moments_kernel, planes, dim3(kEwBlock), 0, st, sv + S.y2, sc + T.part, c, hw);
-      hipLaunchKernelGGL(bn_train_finalize_kernel, per_ch, dim3(kEwBlock), 0, st, sc + T.part, b * kPlaneChunks, sv + S.y2, hw, w->bn2_w,
-                         w->bn2_b, w->bn2_mean, w->bn2_var, w->momentum2, w->eps2, sv + S.mean2, sv + S.rstd2, sv + S.scsh2,
-                         tab_unused, b, c, hw, reinterpret_cast<long long*>(w->bn2_batches));
-    }
   } else {
-    hipLaunchKernelGGL(bn_eval_coef_kernel, per_ch, dim3(kEwBlock), 0, st, w->bn2_w, w->bn2_b, w->bn2_mean, w->bn2_var, w->eps2,
-                       sv + S.mean2, sv + S.rstd2, sv + S.scsh2, tab_unused, b, c);
+    if (storage_dtype != DHD_F16 && storage_dtype != DHD_BF16) return DHD_EINVAL;
+    if (!half_storage_supported(c, hw)) return DHD_EUNSUPPORTED;
   }
-  if (w->io_dtype == DHD_F16)
-    hipLaunchKernelGGL(blend2_bn_kernel<_Float16>, planes, dim3(kEwBlock), 0, st, x, sv + S.a1, sv + S.y2, sv + S.scsh2, static_cast<_Float16*>(out), c, hw);
-  else if (w->io_dtype == DHD_BF16)
-    hipLaunchKernelGGL(blend2_bn_kernel<__bf16>, planes, dim3(kEwBlock), 0, st, x, sv + S.a1, sv + S.y2, sv + S.scsh2, static_cast<__bf16*>(out), c, hw);
-  else
-    hipLaunchKernelGGL(blend2_bn_kernel<float>, planes, dim3(kEwBlock), 0, st, x, sv + S.a1, sv + S.y2, sv + S.scsh2, static_cast<float*>(out), c, hw);
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
-}
-
-// Backward in up to three phases, cut where the two BatchNorm backward passes need their sums (sum g, sum g (y - mu)); `sync`
-// as in stage_forward_impl ((2C + 1) doubles: [sum g][C] | [sum g (y - mu)][C] | count).
-static int stage_backward_impl(const void* xv, const dhd_sfa_weights* w, const void* saved, const void* gout, void* gx,
-                               const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw, int lo, int hi, double* sync,
-                               void* stream) {
-  if (!xv || !w || !saved || !gout || !grads || !scratch || b <= 0 || (hi == 2 && !gx)) return DHD_EINVAL;
-  if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
-  if (!grads->fc1_w || !grads->fc1_b || !grads->fc2_w || !grads->fc2_b || !grads->conv1_w || !grads->conv1_b || !grads->bn1_w ||
-      !grads->bn1_b || !grads->conv2_w || !grads->conv2_b || !grads->bn2_w || !grads->bn2_b)
-    return DHD_EINVAL;
-  if (set_call_mode(w->gemm) != DHD_OK) return DHD_EINVAL;
-  if (w->io_dtype != DHD_F32 && w->io_dtype != DHD_F16 && w->io_dtype != DHD_BF16) return DHD_EINVAL;
-  hipStream_t st = dhd_stream(stream);
-  int storage;
-  if (int rcs = storage_of(w, c, hw, &storage); rcs != DHD_OK) return rcs;
-  if (storage == DHD_F16) return stage_backward_half<_Float16>(xv, w, saved, gout, gx, grads, scratch, b, c, hw, lo, hi, sync, st);
-  if (storage == DHD_BF16) return stage_backward_half<__bf16>(xv, w, saved, gout, gx, grads, scratch, b, c, hw, lo, hi, sync, st);
-  if (sync && !(w->training && g_gemm_mode >= 1)) return DHD_EUNSUPPORTED;
-  const float* x = static_cast<const float*>(xv);
-  const int r = w->hidden;
-  const SavedLayout S = saved_layout(b, c, hw, r);
-  const ScratchLayout T = scratch_layout(b, c, hw, r);
-  const float* sv = static_cast<const float*>(saved);
-  float* sc = static_cast<float*>(scratch);
-  const dim3 planes(kPlaneChunks, b * c);
-  const dim3 per_ch(dhd_cdiv(c, kEwBlock));
-  const size_t cs = (size_t)c * hw;
-  int rc;
-
-  if (lo <= 0) {
-    // g2 = dL/ds2, BatchNorm-2 sums, go-part of dL/da
-    // without cross-rank statistics the pass finishes its own reduction (BnTail): no bn_backward_coef launch
-    int* tick = reinterpret_cast<int*>(const_cast<float*>(sv + S.tick));
-    const BnTail tail2 = {sync ? nullptr : tick, w->bn2_w, sv + S.mean2, sv + S.rstd2, sc + T.tab_g2, grads->bn2_w, grads->bn2_b,
-                          grads->conv2_b, w->training, b, hw};
-#define DHD_B2BWD(TO)                                                                                                        \
-  hipLaunchKernelGGL(blend2_bn_bwd_kernel<TO>, planes, dim3(kEwBlock), 0, st, x, sv + S.a1, sv + S.y2, sv + S.scsh2, sv + S.mean2, \
-                     static_cast<const TO*>(gout), sc + T.g2, sc + T.part, sc + T.da1, c, hw, tail2)
-    if (w->io_dtype == DHD_F16) DHD_B2BWD(_Float16);
-    else if (w->io_dtype == DHD_BF16) DHD_B2BWD(__bf16);
-    else DHD_B2BWD(float);
-#undef DHD_B2BWD
-    if (sync)
-      hipLaunchKernelGGL(bn_backward_coef_kernel, per_ch, dim3(kEwBlock), 0, st, sc + T.part, w->bn2_w, sv + S.mean2, sv + S.rstd2,
-                         w->training, sc + T.tab_g2, grads->bn2_w, grads->bn2_b, grads->conv2_b, b, c, hw, sync, nullptr, nullptr, nullptr);
-    DHD_LAUNCH_CHECK();
-  }
-  if (hi <= 0) return DHD_OK;
-  if (lo <= 1) {
-    if (sync)
-      hipLaunchKernelGGL(bn_backward_coef_kernel, per_ch, dim3(kEwBlock), 0, st, sc + T.part, w->bn2_w, sv + S.mean2, sv + S.rstd2,
-                         w->training, sc + T.tab_g2, grads->bn2_w, grads->bn2_b, grads->conv2_b, b, c, hw, nullptr, sync,
-                         reinterpret_cast<const double*>(sv + S.loc2), w->conv2_b);
-    DHD_LAUNCH_CHECK();
-    // dW2 = dy2 . z1^T
-    rc = launch_pw_wgrad(sc + T.g2, sv + S.y2, sc + T.tab_g2, cs, sv + S.y1, nullptr, sv + S.tab1, cs, true, sc + T.wpart,
-                         grads->conv2_w, b, c, hw, st);
-    if (rc != DHD_OK) return rc;
-    // g1 = (W2^T dy2) * [z1 > 0]
-    rc = launch_pw_gemm(sc + T.g2, sv + S.y2, cs, c, sc + T.tab_g2, false, sv + S.wp2t, nullptr, sv + S.y1, sv + S.scsh1,
-                        reinterpret_cast<unsigned*>(const_cast<float*>(sv + S.mask)), nullptr, sc + T.g1, 1, b,
-                        c, hw, st);
-    if (rc != DHD_OK) return rc;
-    int* tick = reinterpret_cast<int*>(const_cast<float*>(sv + S.tick)) + c;
-    const BnTail tail1 = {sync ? nullptr : tick, w->bn1_w, sv + S.mean1, sv + S.rstd1, sc + T.tab_g1, grads->bn1_w, grads->bn1_b,
-                          grads->conv1_b, w->training, b, hw};
-    hipLaunchKernelGGL(pair_sums_kernel, planes, dim3(kEwBlock), 0, st, sc + T.g1, sv + S.y1, sv + S.mean1, sc + T.part, c, hw, tail1);
-    if (sync)
-      hipLaunchKernelGGL(bn_backward_coef_kernel, per_ch, dim3(kEwBlock), 0, st, sc + T.part, w->bn1_w, sv + S.mean1, sv + S.rstd1,
-                         w->training, sc + T.tab_g1, grads->bn1_w, grads->bn1_b, grads->conv1_b, b, c, hw, sync, nullptr, nullptr, nullptr);
-    DHD_LAUNCH_CHECK();
-  }
-  if (hi <= 1) return DHD_OK;
-  if (sync)
-    hipLaunchKernelGGL(bn_backward_coef_kernel, per_ch, dim3(kEwBlock), 0, st, sc + T.part, w->bn1_w, sv + S.mean1, sv + S.rstd1,
-                       w->training, sc + T.tab_g1, grads->bn1_w, grads->bn1_b, grads->conv1_b, b, c, hw, nullptr, sync,
-                       reinterpret_cast<const double*>(sv + S.loc1), w->conv1_b);
-  DHD_LAUNCH_CHECK();
-  // dW1 = dy1 . u^T
-  rc = launch_pw_wgrad(sc + T.g1, sv + S.y1, sc + T.tab_g1, cs, x, x + cs, sv + S.tab_a, 2 * cs, false, sc + T.wpart, grads->conv1_w,
-                       b, c, hw, st);
-  if (rc != DHD_OK) return rc;
-  // du = W1^T dy1
-  rc = launch_pw_gemm(sc + T.g1, sv + S.y1, cs, c, sc + T.tab_g1, false, sv + S.wp1t, nullptr, nullptr, nullptr, nullptr, nullptr, sc + T.du, 2, b, c,
-                      hw, st);
-  if (rc != DHD_OK) return rc;
-  hipLaunchKernelGGL(blend1_da_kernel, planes, dim3(kEwBlock), 0, st, x, sc + T.du, sc + T.da2, c, hw);
-  hipLaunchKernelGGL(fc_backward_kernel, dim3(b), dim3(kEwBlock), (size_t)(c + r + kEwBlock) * sizeof(float), st, sc + T.da1, sc + T.da2,
-                     sv + S.a1, sv + S.h, w->fc1_w, w->fc2_w, sc + T.dpre2, sc + T.dh, sc + T.ds, c, r);
-  const int n_fc = r * 2 * c + c * r + r + c;
-  const FcGradJob fcj = {sc + T.dpre2, sc + T.dh, sv + S.h, sv + S.s, grads->fc1_w, grads->fc1_b, grads->fc2_w, grads->fc2_b, b, r};
-  const int fc_rows = dhd_cdiv(dhd_cdiv(n_fc, kEwBlock), kPlaneChunks);
-  const dim3 planes_fc(kPlaneChunks, b * c + fc_rows);
-#define DHD_GX(TO)                                                                                                           \
-  hipLaunchKernelGGL(stage_gx_kernel<TO>, planes_fc, dim3(kEwBlock), 0, st, sv + S.a1, sv + S.y2, sv + S.scsh2,                 \
-                     static_cast<const TO*>(gout), sc + T.du, sc + T.ds, static_cast<TO*>(gx), c, hw, fc_rows, fcj)
-  if (w->io_dtype == DHD_F16) DHD_GX(_Float16);
-  else if (w->io_dtype == DHD_BF16) DHD_GX(__bf16);
-  else DHD_GX(float);
-#undef DHD_GX
-  DHD_LAUNCH_CHECK();
+  *saved_bytes = saved_layout(b, c, hw, hidden, storage_dtype).total;
+  *scratch_bytes = scratch_layout(b, c, hw, hidden, storage_dtype).total;
   return DHD_OK;
 }
 
 int dhd_sfa_stage_forward(const void* x, const dhd_sfa_weights* w, void* out, void* saved, void* scratch, int b, int c, int hw,
                           void* stream) {
-  return stage_forward_impl(x, w, out, saved, scratch, b, c, hw, 0, 2, nullptr, stream);
+  return stage_forward_entry(x, w, out, saved, scratch, b, c, hw, 0, 2, nullptr, stream);
 }
 
 int dhd_sfa_stage_backward(const void* x, const dhd_sfa_weights* w, const void* saved, const void* gout, void* gx,
                            const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw, void* stream) {
-  return stage_backward_impl(x, w, saved, gout, gx, grads, scratch, b, c, hw, 0, 2, nullptr, stream);
+  return stage_backward_entry(x, w, saved, gout, gx, grads, scratch, b, c, hw, 0, 2, nullptr, stream);
 }
 
 int dhd_sfa_stage_forward_phase(const void* x, const dhd_sfa_weights* w, void* out, void* saved, void* scratch, int b, int c, int hw,
                                 int phase, double* sync_sums, void* stream) {
   if (phase < 0 || phase > 2 || !sync_sums || (reinterpret_cast<uintptr_t>(sync_sums) & 7)) return DHD_EINVAL;
-  return stage_forward_impl(x, w, out, saved, scratch, b, c, hw, phase, phase, sync_sums, stream);
+  return stage_forward_entry(x, w, out, saved, scratch, b, c, hw, phase, phase, sync_sums, stream);
 }
 
 int dhd_sfa_stage_backward_phase(const void* x, const dhd_sfa_weights* w, const void* saved, const void* gout, void* gx,
                                  const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw, int phase, double* sync_sums,
                                  void* stream) {
   if (phase < 0 || phase > 2 || !sync_sums || (reinterpret_cast<uintptr_t>(sync_sums) & 7)) return DHD_EINVAL;
-  return stage_backward_impl(x, w, saved, gout, gx, grads, scratch, b, c, hw, phase, phase, sync_sums, stream);
+  return stage_backward_entry(x, w, saved, gout, gx, grads, scratch, b, c, hw, phase, phase, sync_sums, stream);
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../dhd_amd/csrc/sfa_stage.hip"   // the whole product translation unit: launch_pw_gemm_res (anonymous namespace) for the A/B
+#include "../dhd_amd/csrc/sfa_stage.hip"   // the whole product translation unit (its helpers live in an anonymous namespace)
 #include "../dhd_amd/csrc/sfa_gemm_cu.h"
 
 using namespace dhd_sfa;
@@ -162,17 +162,9 @@ int main(int argc, char** argv) {
   RUNP(8, true, false, 0, false, 2, 1, 1, 0, 0, true, 1, "8w conv1 (bias+stats), PING-PONG");
   RUNP(8, false, true, 0, true, 2, 1, 1, 0, 0, true, 1, "8w conv2 (relu+record), PING-PONG");
   RUNP(8, true, false, 1, false, 2, 1, 1, 0, 0, true, 1, "8w dgrad2 (mask), PING-PONG");
-  // ---- A/B against the resident-weights kernel of the product (teams of two CUs), alternating, same process ---------------
+  // ---- A/B of the epilogue order and the B-fragment prefetch, alternating, same process (the resident-weights column of round 3
+  // is gone: the product no longer builds pw_gemm_res for bf16x3 at C = 128 / 256) ----------------------------------------------
   {
-    float* wpres; float* statres;
-    CK(hipMalloc(&wpres, (size_t)2 * C * C * 4)); CK(hipMalloc(&statres, (size_t)B * (HW / 32 + 64) * 2 * C * 4));
-    g_gemm_mode = 3;
-    hipLaunchKernelGGL(pack_weight_res_kernel, dim3(dhd_cdiv((C / 32) * (C / 16) * 64, kEwBlock), 1), dim3(kEwBlock), 0, 0, w, nullptr, 0,
-                       reinterpret_cast<u32x4*>(wpres), nullptr, C, res_cob(C, 2), 2);
-    CK(hipDeviceSynchronize());
-    auto old_conv1 = [&] { int rows; launch_pw_gemm_res(x, x + plane, 2 * plane, C, coef, false, wpres, bias, nullptr, statres, y, 0, B, C, HW, 0, &rows); };
-    auto old_dgrad = [&] { int rows; launch_pw_gemm_res(x, x + plane, 2 * plane, C, coef, false, wpres, nullptr, nullptr, nullptr, y, 2, B, C, HW, 0, &rows); };
-    auto old_conv2 = [&] { int rows; launch_pw_gemm_res(x, nullptr, 2 * plane, C, coef, true, wpres, bias, mask, statres, y, 0, B, C, HW, 0, &rows); };
 #define NEWK(WAVES, TWO, RELU, EPI, REC, AUX, RR, NACC, contig) NEWP(WAVES, TWO, RELU, EPI, REC, AUX, RR, NACC, false, contig)
 #define NEWP(WAVES, TWO, RELU, EPI, REC, AUX, RR, NACC, PP, contig) NEWQ(WAVES, TWO, RELU, EPI, REC, AUX, RR, NACC, PP, 0, 0, contig)
 #define NEWQ(WAVES, TWO, RELU, EPI, REC, AUX, RR, NACC, PP, BPF, EORD, contig)                                                            \
@@ -195,10 +187,10 @@ int main(int argc, char** argv) {
     auto d2_0 = NEWQ(8, true, false, 1, false, 2, 1, 1, true, 0, 1, 1);
     auto blend = [&] { hipLaunchKernelGGL(blend_kernel, dim3(cus * 8), dim3(512), 0, 0, (f32x4*)x, (f32x4*)(x + (size_t)B * plane), (f32x4*)y, (size_t)B * plane / 4, 0.5f, 0.25f); };
     for (int round = 0; round < 4; ++round) {
-      printf("round %d:  blend %.1f | conv1 old %.1f epi-first bpf0 %.1f bpf1 %.1f | dgrad old %.1f epi-first bpf0 %.1f bpf1 %.1f epi-last bpf0 %.1f dgrad2 %.1f | conv2 old %.1f epi-first bpf0 %.1f bpf1 %.1f epi-last bpf0 %.1f  (us)\n", round,
-             time_kernel(blend, 7), time_kernel(old_conv1, 7), time_kernel(c1_0, 7), time_kernel(c1_1, 7),
-             time_kernel(old_dgrad, 7), time_kernel(dg_0, 7), time_kernel(dg_1, 7), time_kernel(dg_00, 7), time_kernel(d2_0, 7),
-             time_kernel(old_conv2, 7), time_kernel(c2_0, 7), time_kernel(c2_1, 7), time_kernel(c2_00, 7));
+      printf("round %d:  blend %.1f | conv1 epi-first bpf0 %.1f bpf1 %.1f | dgrad epi-first bpf0 %.1f bpf1 %.1f epi-last bpf0 %.1f dgrad2 %.1f | conv2 epi-first bpf0 %.1f bpf1 %.1f epi-last bpf0 %.1f  (us)\n", round,
+             time_kernel(blend, 7), time_kernel(c1_0, 7), time_kernel(c1_1, 7),
+             time_kernel(dg_0, 7), time_kernel(dg_1, 7), time_kernel(dg_00, 7), time_kernel(d2_0, 7),
+             time_kernel(c2_0, 7), time_kernel(c2_1, 7), time_kernel(c2_00, 7));
       CK(hipGetLastError());
     }
   }

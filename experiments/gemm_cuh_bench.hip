@@ -161,25 +161,26 @@ static void run(const char* tname, int B, int HW, int C) {
   };
   hipStream_t st = 0;
   int rows = 0;
+  const Plan plan{};   // launch_wgrad<half type> always runs pw_wgrad_h
   printf("%s  B %d  HW %d  C %d\n", tname, B, HW, C);
   // conv1: two inputs, bias + statistics
   CK(hipMemset(y, 0xff, (size_t)B * plane * 2));
-  if (launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wp, bias, nullptr, stat, y, 0, B, C, HW, st, &rows)) printf("launch failed\n");
+  if (launch_gemm_cu<TS>({kConv1, x, x + plane, 2 * plane, C, coef, wp, bias, nullptr, stat, y}, B, C, HW, st, &rows)) printf("launch failed\n");
   CK(hipDeviceSynchronize());
   check("conv1 (two in, EPI 0)", x, x + plane, 2 * plane, 0, 0, bias, 0, false);
   check("conv1 channels 120..127", x, x + plane, 2 * plane, 0, 0, bias, C - 8, false);
   // conv2: one input, relu, record
   CK(hipMemset(y, 0xff, (size_t)B * plane * 2));
-  if (launch_pw_gemm_cuh<TS>(g, (const TS*)nullptr, plane, C, coef, true, wp, bias, mask, stat, y, 0, B, C, HW, st, &rows)) printf("launch failed\n");
+  if (launch_gemm_cu<TS>({kConv2, g, (const TS*)nullptr, plane, C, coef, wp, bias, mask, stat, y}, B, C, HW, st, &rows)) printf("launch failed\n");
   CK(hipDeviceSynchronize());
   check("conv2 (relu, record, EPI 0)", g, nullptr, plane, 1, 0, bias, 40, false);
   // dgrad with mask
   CK(hipMemset(y, 0xff, (size_t)B * plane * 2));
-  if (launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wpt, nullptr, mask, nullptr, y, 1, B, C, HW, st, nullptr)) printf("launch failed\n");
+  if (launch_gemm_cu<TS>({kDgrad2, x, x + plane, 2 * plane, C, coef, wpt, nullptr, mask, nullptr, y}, B, C, HW, st, nullptr)) printf("launch failed\n");
   CK(hipDeviceSynchronize());
   check("dgrad 2 (EPI 1, W^T)", x, x + plane, 2 * plane, 0, 1, nullptr, 64, true);
   CK(hipMemset(y, 0xff, (size_t)B * plane * 2));
-  if (launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wpt, nullptr, nullptr, nullptr, y, 2, B, C, HW, st, nullptr)) printf("launch failed\n");
+  if (launch_gemm_cu<TS>({kDgrad1, x, x + plane, 2 * plane, C, coef, wpt, nullptr, nullptr, nullptr, y}, B, C, HW, st, nullptr)) printf("launch failed\n");
   CK(hipDeviceSynchronize());
   check("dgrad 1 (EPI 2, W^T)", x, x + plane, 2 * plane, 0, 1, nullptr, 96, false);
 
@@ -201,10 +202,10 @@ static void run(const char* tname, int B, int HW, int C) {
       }
     printf("  %-28s max |err| %.3e (scale %.1f)\n", what, worst, scale);
   };
-  if (launch_pw_wgrad_h<TS>(x, x + plane, coef, 2 * plane, g, (const TS*)nullptr, coef, plane, true, partial, gw, B, C, HW, st)) printf("launch failed\n");
+  if (launch_wgrad<TS>(plan, kConv2, x, x + plane, coef, 2 * plane, g, (const TS*)nullptr, coef, plane, partial, gw, B, C, HW, st)) printf("launch failed\n");
   CK(hipDeviceSynchronize());
   check_w("wgrad (B relu)", g, nullptr, plane, 1, 16);
-  if (launch_pw_wgrad_h<TS>(x, x + plane, coef, 2 * plane, x, x + plane, coef, 2 * plane, false, partial, gw, B, C, HW, st)) printf("launch failed\n");
+  if (launch_wgrad<TS>(plan, kConv1, x, x + plane, coef, 2 * plane, x, x + plane, coef, 2 * plane, partial, gw, B, C, HW, st)) printf("launch failed\n");
   CK(hipDeviceSynchronize());
   check_w("wgrad (B two in)", x, x + plane, 2 * plane, 0, C - 8);
 
@@ -212,12 +213,12 @@ static void run(const char* tname, int B, int HW, int C) {
   const size_t n16 = (size_t)B * plane * 2 / 16;
   const double t_blend = time_kernel([&] { blend_kernel<<<2048, 256>>>((const u32x4*)x, (const u32x4*)g, (u32x4*)y, n16); });
   printf("  blend floor (read 2, write 1 planes of %zu MB): %.1f us = %.2f TB/s\n", (size_t)B * plane * 2 >> 20, t_blend, 3.0 * B * plane * 2 / t_blend / 1e6);
-  printf("  conv1  %.1f us\n", time_kernel([&] { launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wp, bias, nullptr, stat, y, 0, B, C, HW, st, &rows); }));
-  printf("  conv2  %.1f us\n", time_kernel([&] { launch_pw_gemm_cuh<TS>(g, (const TS*)nullptr, plane, C, coef, true, wp, bias, mask, stat, y, 0, B, C, HW, st, &rows); }));
-  printf("  dgrad2 %.1f us\n", time_kernel([&] { launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wpt, nullptr, mask, nullptr, y, 1, B, C, HW, st, nullptr); }));
-  printf("  dgrad1 %.1f us\n", time_kernel([&] { launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wpt, nullptr, nullptr, nullptr, y, 2, B, C, HW, st, nullptr); }));
-  printf("  wgrad2 (+reduce) %.1f us\n", time_kernel([&] { launch_pw_wgrad_h<TS>(x, x + plane, coef, 2 * plane, g, (const TS*)nullptr, coef, plane, true, partial, gw, B, C, HW, st); }));
-  printf("  wgrad1 (+reduce) %.1f us\n", time_kernel([&] { launch_pw_wgrad_h<TS>(x, x + plane, coef, 2 * plane, x, x + plane, coef, 2 * plane, false, partial, gw, B, C, HW, st); }));
+  printf("  conv1  %.1f us\n", time_kernel([&] { launch_gemm_cu<TS>({kConv1, x, x + plane, 2 * plane, C, coef, wp, bias, nullptr, stat, y}, B, C, HW, st, &rows); }));
+  printf("  conv2  %.1f us\n", time_kernel([&] { launch_gemm_cu<TS>({kConv2, g, (const TS*)nullptr, plane, C, coef, wp, bias, mask, stat, y}, B, C, HW, st, &rows); }));
+  printf("  dgrad2 %.1f us\n", time_kernel([&] { launch_gemm_cu<TS>({kDgrad2, x, x + plane, 2 * plane, C, coef, wpt, nullptr, mask, nullptr, y}, B, C, HW, st, nullptr); }));
+  printf("  dgrad1 %.1f us\n", time_kernel([&] { launch_gemm_cu<TS>({kDgrad1, x, x + plane, 2 * plane, C, coef, wpt, nullptr, nullptr, nullptr, y}, B, C, HW, st, nullptr); }));
+  printf("  wgrad2 (+reduce) %.1f us\n", time_kernel([&] { launch_wgrad<TS>(plan, kConv2, x, x + plane, coef, 2 * plane, g, (const TS*)nullptr, coef, plane, partial, gw, B, C, HW, st); }));
+  printf("  wgrad1 (+reduce) %.1f us\n", time_kernel([&] { launch_wgrad<TS>(plan, kConv1, x, x + plane, coef, 2 * plane, x, x + plane, coef, 2 * plane, partial, gw, B, C, HW, st); }));
   CK(hipFree(x)); CK(hipFree(y)); CK(hipFree(g)); CK(hipFree(yref)); CK(hipFree(gref)); CK(hipFree(partial));
 }
 

@@ -63,6 +63,67 @@ def test_sfa_stage_shape_support_and_validation():
     assert _lib.SFA_GEMM == {'default': 0, 'bf16x6': 1, 'f32': 2, 'bf16x3': 3}
 
 
+# (b, C, hw) -> saved / scratch bytes of float32 storage, then of half storage (fp16 and bf16 alike; None: unsupported), as the
+# library returned them before its host side was rewritten.  hw = 40 and 1368 are not multiples of 32 or 64.  hidden = 32.
+SFA_WORKSPACE_BYTES = {
+    (1, 128, 40): (318976, 17185536, 101888, 18987776),
+    (1, 128, 1368): (1699840, 19267328, 803328, 20007680),
+    (1, 128, 40000): (41876992, 79842048, 21200384, 49677056),
+    (4, 128, 40): (459008, 17623552, 180480, 19130880),
+    (4, 128, 1368): (5982464, 25950720, 2986240, 23210496),
+    (4, 128, 40000): (166691072, 268249600, 84574464, 141888000),
+    (9, 128, 40): (692736, 18353920, 311808, 20418304),
+    (9, 128, 1368): (13120512, 37090048, 6624768, 29597440),
+    (9, 128, 40000): (374714880, 582262528, 190198272, 296621824),
+    (1, 256, 40): (1161216, 68449536, 333824, 71660800),
+    (1, 256, 1368): (3922944, 72613120, 1736704, 73700608),
+    (1, 256, 40000): (84277248, 193762560, 42530816, 133039360),
+    (4, 256, 40): (1441024, 69325312, 490752, 71946752),
+    (4, 256, 1368): (12487936, 85979648, 6102272, 80105984),
+    (4, 256, 40000): (333905152, 570577408, 169278720, 317460992),
+    (9, 256, 40): (1907712, 70785280, 752640, 74520832),
+    (9, 256, 1368): (26763264, 108257536, 13378560, 92879104),
+    (9, 256, 40000): (749952000, 1198602496, 380525568, 626927872),
+    (1, 512, 40): (4418560, 273213696, None, None),
+    (1, 512, 1368): (9942016, 281540864, None, None),
+    (1, 512, 40000): (170650624, 523839744, None, None),
+    (4, 512, 40): (4977920, 274964992, None, None),
+    (4, 512, 1368): (27071744, 308273664, None, None),
+    (4, 512, 40000): (669906176, 1277469184, None, None),
+    (9, 512, 40): (5910528, 277884160, None, None),
+    (9, 512, 1368): (55621632, 352828672, None, None),
+    (9, 512, 40000): (1501999104, 2533518592, None, None),
+    (1, 768, 40): (9773056, 614292736, None, None),
+    (1, 768, 1368): (18058240, 626783488, None, None),
+    (1, 768, 40000): (259121152, 990231808, None, None),
+    (4, 768, 40): (10611968, 616919552, None, None),
+    (4, 768, 1368): (43752704, 666882560, None, None),
+    (4, 768, 40000): (1008004352, 2120675840, None, None),
+    (9, 768, 40): (12010496, 621297920, None, None),
+    (9, 768, 1368): (86577152, 733714688, None, None),
+    (9, 768, 40000): (2256143360, 4004749568, None, None),
+}
+
+
+def test_sfa_stage_workspace_bytes_are_pinned():
+    """dhd_sfa_stage_workspace_bytes / _saved_bytes / _scratch_bytes: captured graphs and caches are sized from them, so a layout
+    change must be deliberate."""
+    from dhd_amd import _lib
+    lib = _lib.load()
+    s, t = C.c_size_t(0), C.c_size_t(0)
+    for (b, c, hw), (fs, ft, hs, ht) in SFA_WORKSPACE_BYTES.items():
+        assert lib.dhd_sfa_stage_workspace_bytes(b, c, hw, 32, 0, C.byref(s), C.byref(t)) == 0
+        assert (s.value, t.value) == (fs, ft), (b, c, hw)
+        assert (lib.dhd_sfa_stage_saved_bytes(b, c, hw, 32), lib.dhd_sfa_stage_scratch_bytes(b, c, hw, 32)) == (fs, ft), (b, c, hw)
+        for storage in (1, 2):   # DHD_F16, DHD_BF16
+            rc = lib.dhd_sfa_stage_workspace_bytes(b, c, hw, 32, storage, C.byref(s), C.byref(t))
+            if hs is None:
+                assert rc == -3, (b, c, hw, storage)
+            else:
+                assert rc == 0 and (s.value, t.value) == (hs, ht), (b, c, hw, storage)
+        assert lib.dhd_sfa_stage_workspace_bytes(b, c, hw, 32, 5, C.byref(s), C.byref(t)) == -1
+
+
 def test_library_is_a_gfx950_code_object():
     from dhd_amd import _lib
     blob = open(_lib.LIB_PATH, 'rb').read()
