@@ -48,15 +48,12 @@ class TensorView(C.Structure):
                 ('dtype', C.c_int32)]
 
 
-DTYPE_CODE = {}   # torch dtype -> dhd_tensor_view.dtype (filled on first use: torch is imported lazily by some callers)
+DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # torch dtype -> DHD_F32 / DHD_F16 / DHD_BF16 of the C ABI
 
 
 def dtype_code(dt):
-    import torch
-    if not DTYPE_CODE:
-        DTYPE_CODE.update({torch.float32: 0, torch.float16: 1, torch.bfloat16: 2})
     if dt not in DTYPE_CODE:
-        raise DhdError(f'pooled tensors are float32, float16 or bfloat16, not {dt}')
+        raise DhdError(f'the library takes float32, float16 or bfloat16 tensors, not {dt}')
     return DTYPE_CODE[dt]
 
 

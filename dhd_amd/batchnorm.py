@@ -11,7 +11,6 @@ from torch import nn
 
 from . import _lib
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 class _BNTrain(torch.autograd.Function):
@@ -26,7 +25,7 @@ class _BNTrain(torch.autograd.Function):
             mean = torch.empty(c, dtype=torch.float32, device=dev)
             rstd = torch.empty_like(mean)
             ws = torch.empty(lib.dhd_bn_workspace_bytes(n, c, hw), dtype=torch.uint8, device=dev)
-            _lib.check(lib.dhd_bn_train_forward(_lib.ptr(x), _DTYPES[x.dtype], n, c, hw, _lib.ptr(weight), _lib.ptr(bias),
+            _lib.check(lib.dhd_bn_train_forward(_lib.ptr(x), _lib.dtype_code(x.dtype), n, c, hw, _lib.ptr(weight), _lib.ptr(bias),
                                                 _lib.ptr(running_mean), _lib.ptr(running_var), factor, eps, _lib.ptr(y), _lib.ptr(mean),
                                                 _lib.ptr(rstd), _lib.ptr(ws), _lib.stream_ptr(dev)), 'dhd_bn_train_forward')
         ctx.save_for_backward(x, weight, mean, rstd)
@@ -48,7 +47,7 @@ class _BNTrain(torch.autograd.Function):
             dgamma = torch.empty(c, dtype=torch.float32, device=dev)
             dbeta = torch.empty_like(dgamma)
             ws = torch.empty(lib.dhd_bn_workspace_bytes(n, c, hw), dtype=torch.uint8, device=dev)
-            _lib.check(lib.dhd_bn_train_backward(_lib.ptr(x), _lib.ptr(gy), _DTYPES[x.dtype], n, c, hw, _lib.ptr(weight), _lib.ptr(mean),
+            _lib.check(lib.dhd_bn_train_backward(_lib.ptr(x), _lib.ptr(gy), _lib.dtype_code(x.dtype), n, c, hw, _lib.ptr(weight), _lib.ptr(mean),
                                                  _lib.ptr(rstd), _lib.ptr(gx), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws),
                                                  _lib.stream_ptr(dev)), 'dhd_bn_train_backward')
         gw = dgamma.to(weight.dtype) if weight is not None and ctx.needs_input_grad[1] else None
@@ -79,7 +78,7 @@ class _BNTrainNHWC(torch.autograd.Function):
             rstd = torch.empty_like(mean)
             affine = torch.empty(2 * c, dtype=torch.float32, device=dev)
             ws = torch.empty(lib.dhd_bn_nhwc_workspace_bytes(rows, c), dtype=torch.uint8, device=dev)
-            _lib.check(lib.dhd_bn_nhwc_train_forward(_lib.ptr(x), _lib.ptr(residual), _DTYPES[x.dtype], rows, c, flags, _lib.ptr(weight),
+            _lib.check(lib.dhd_bn_nhwc_train_forward(_lib.ptr(x), _lib.ptr(residual), _lib.dtype_code(x.dtype), rows, c, flags, _lib.ptr(weight),
                                                      _lib.ptr(bias), _lib.ptr(running_mean), _lib.ptr(running_var), factor, eps, _lib.ptr(y),
                                                      _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(affine), _lib.ptr(ws), _lib.stream_ptr(dev)),
                        'dhd_bn_nhwc_train_forward')
@@ -104,7 +103,7 @@ class _BNTrainNHWC(torch.autograd.Function):
             dgamma = torch.empty(c, dtype=torch.float32, device=dev)
             dbeta = torch.empty_like(dgamma)
             ws = torch.empty(lib.dhd_bn_nhwc_workspace_bytes(rows, c), dtype=torch.uint8, device=dev)
-            _lib.check(lib.dhd_bn_nhwc_train_backward(_lib.ptr(x), _lib.ptr(y), _lib.ptr(gy), _DTYPES[x.dtype], rows, c, ctx.flags,
+            _lib.check(lib.dhd_bn_nhwc_train_backward(_lib.ptr(x), _lib.ptr(y), _lib.ptr(gy), _lib.dtype_code(x.dtype), rows, c, ctx.flags,
                                                       _lib.ptr(weight), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(affine), _lib.ptr(gx),
                                                       _lib.ptr(gres), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), _lib.stream_ptr(dev)),
                        'dhd_bn_nhwc_train_backward')
@@ -169,7 +168,7 @@ class BatchNorm2d(nn.BatchNorm2d):
         return cls._routing
 
     def _hip_ok(self, x, force=False):
-        if not (self.use_hip and self.training and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and x.numel() > 0):
+        if not (self.use_hip and self.training and x.is_cuda and x.dim() == 4 and x.dtype in _lib.DTYPE_CODE and x.numel() > 0):
             return False
         if not force and not x.is_contiguous():   # channels_last activations stay with the layout-preserving library path
             return False
@@ -183,12 +182,12 @@ class BatchNorm2d(nn.BatchNorm2d):
         if self.track_running_stats and self.running_mean.dtype != torch.float32:
             return False
         n, c = x.shape[:2]
-        return bool(_lib.load().dhd_bn_supported(_DTYPES[x.dtype], n, c, x[0, 0].numel()))
+        return bool(_lib.load().dhd_bn_supported(_lib.dtype_code(x.dtype), n, c, x[0, 0].numel()))
 
     use_nhwc = not os.environ.get('DHD_BN_NO_NHWC')   # A/B switch: channels_last tensors go to the library's kernels
 
     def _nhwc_ok(self, x):
-        if not (self.use_hip and self.use_nhwc and self.training and x.is_cuda and x.dtype in _DTYPES and x.numel() > 0 and _is_nhwc(x)
+        if not (self.use_hip and self.use_nhwc and self.training and x.is_cuda and x.dtype in _lib.DTYPE_CODE and x.numel() > 0 and _is_nhwc(x)
                 and x.data_ptr() % 16 == 0):      # 16-byte vector loads / stores
             return False
         if self.weight is not None and (self.weight.dtype != torch.float32 or (self.bias is not None and self.bias.dtype != torch.float32)):
@@ -196,7 +195,7 @@ class BatchNorm2d(nn.BatchNorm2d):
         if self.track_running_stats and self.running_mean.dtype != torch.float32:
             return False
         n, c, h, w = x.shape
-        return bool(_lib.load().dhd_bn_nhwc_supported(_DTYPES[x.dtype], n * h * w, c))
+        return bool(_lib.load().dhd_bn_nhwc_supported(_lib.dtype_code(x.dtype), n * h * w, c))
 
     def forward(self, x, relu=False, residual=None):
         """`relu` / `residual`: the caller's `relu(bn(x))` or `relu(bn(x) + residual)` (resnet.py:282-300, mmcv's ConvModule) in

@@ -4,85 +4,15 @@
 // MIOpen's kernels, which move these tensors at 0.7-3.6 TB/s).  Forward: plane sums -> per-channel finalize
 // (double) -> y = x * scale + shift.  Backward: plane sums of g and g * (x - mean) -> coefficients ->
 // gx = c0 * g + c1 * x + c2.  Every pass streams 16-byte vectors; eight passes over the tensor in total.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+#include "vec16.h"
 
 namespace {
 
 constexpr int kBnBlock = 256;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// 16 bytes of activations <-> float lanes
-template <typename T>
-struct Vec;
-template <>
-struct Vec<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    const f32x4 t = {v[0], v[1], v[2], v[3]};
-    __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(p));
-  }
-  static __device__ __forceinline__ float rnd(float f) { return f; }   // the value `store` leaves in memory
-};
-template <>
-struct Vec<__half> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ void load(const __half* p, float (&v)[8]) {
-    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned w = t[i];
-      const __half2 h = *reinterpret_cast<const __half2*>(&w);
-      v[2 * i] = __low2float(h);
-      v[2 * i + 1] = __high2float(h);
-    }
-  }
-  static __device__ __forceinline__ void store(__half* p, const float (&v)[8]) {
-    u32x4 t;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const __half2 h = __floats2half2_rn(v[2 * i], v[2 * i + 1]);
-      t[i] = *reinterpret_cast<const unsigned*>(&h);
-    }
-    __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
-  }
-  static __device__ __forceinline__ float rnd(float f) { return __half2float(__float2half_rn(f)); }
-};
-template <>
-struct Vec<__hip_bfloat16> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&v)[8]) {
-    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(t[i] << 16);
-      v[2 * i + 1] = __uint_as_float(t[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ void store(__hip_bfloat16* p, const float (&v)[8]) {
-    u32x4 t;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      auto rne = [](float f) {  // round to nearest even, as PyTorch's float -> bfloat16
-        const unsigned u = __float_as_uint(f);
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-      };
-      t[i] = rne(v[2 * i]) | (rne(v[2 * i + 1]) << 16);
-    }
-    __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
-  }
-  static __device__ __forceinline__ float rnd(float f) {
-    const unsigned u = __float_as_uint(f);
-    return __uint_as_float(((u + 0x7fffu + ((u >> 16) & 1u)) >> 16) << 16);
-  }
-};
+// 16 bytes of activations <-> float lanes, streamed non-temporally
+template <typename T> using Vec = dhd::Vec16<T, true>;
+// the value Vec<T>::store leaves in memory
+template <typename T> __device__ __forceinline__ float rnd(float f) { return dhd::round2<T>(dhd::f32x2{f, f}).x; }
 
 __device__ __forceinline__ float block_sum(float v, float* sm) {
   v = group_sum(v, DHD_WAVE);
@@ -313,7 +243,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_sums(const T* __restrict__ x, 
         const float da = a[k] - sh[k];
         if (BWD) {
           float gg = ga[k];
-          if (MASK == 1) gg = Vec<T>::rnd(fmaf(f0[k], a[k], f1[k])) > 0.f ? gg : 0.f;
+          if (MASK == 1) gg = rnd<T>(fmaf(f0[k], a[k], f1[k])) > 0.f ? gg : 0.f;
           if (MASK == 2) gg = ya[k] > 0.f ? gg : 0.f;
           s1[k] += gg;
           s2[k] = fmaf(gg, da, s2[k]);
@@ -503,7 +433,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_apply_bwd(const T* __restrict_
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       float gg = ga[k];
-      if (MASK == 1) gg = Vec<T>::rnd(fmaf(f0[k], a[k], f1[k])) > 0.f ? gg : 0.f;
+      if (MASK == 1) gg = rnd<T>(fmaf(f0[k], a[k], f1[k])) > 0.f ? gg : 0.f;
       if (MASK == 2) gg = ya[k] > 0.f ? gg : 0.f;
       gm[k] = gg;
       out[k] = fmaf(c0[k], gg, fmaf(c1[k], a[k], c2[k]));
@@ -599,11 +529,10 @@ int dhd_bn_train_forward(const void* x, int dtype, int n, int c, int hw, const f
   if (!dhd_bn_supported(dtype, n, c, hw)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);
-  switch (dtype) {
-    case 0: return bn_forward_t<float>((const float*)x, n, c, hw, gamma, beta, running_mean, running_var, factor, eps, (float*)y, save_mean, save_rstd, ws, st);
-    case 1: return bn_forward_t<__half>((const __half*)x, n, c, hw, gamma, beta, running_mean, running_var, factor, eps, (__half*)y, save_mean, save_rstd, ws, st);
-    default: return bn_forward_t<__hip_bfloat16>((const __hip_bfloat16*)x, n, c, hw, gamma, beta, running_mean, running_var, factor, eps, (__hip_bfloat16*)y, save_mean, save_rstd, ws, st);
-  }
+  return dhd::with_dtype<dhd::HipHalf>(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return bn_forward_t<T>((const T*)x, n, c, hw, gamma, beta, running_mean, running_var, factor, eps, (T*)y, save_mean, save_rstd, ws, st);
+  });
 }
 
 int dhd_bn_train_backward(const void* x, const void* grad_y, int dtype, int n, int c, int hw, const float* gamma, const float* save_mean,
@@ -612,11 +541,10 @@ int dhd_bn_train_backward(const void* x, const void* grad_y, int dtype, int n, i
   if (!dhd_bn_supported(dtype, n, c, hw)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);
-  switch (dtype) {
-    case 0: return bn_backward_t<float>((const float*)x, (const float*)grad_y, n, c, hw, gamma, save_mean, save_rstd, (float*)grad_x, dgamma, dbeta, ws, st);
-    case 1: return bn_backward_t<__half>((const __half*)x, (const __half*)grad_y, n, c, hw, gamma, save_mean, save_rstd, (__half*)grad_x, dgamma, dbeta, ws, st);
-    default: return bn_backward_t<__hip_bfloat16>((const __hip_bfloat16*)x, (const __hip_bfloat16*)grad_y, n, c, hw, gamma, save_mean, save_rstd, (__hip_bfloat16*)grad_x, dgamma, dbeta, ws, st);
-  }
+  return dhd::with_dtype<dhd::HipHalf>(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return bn_backward_t<T>((const T*)x, (const T*)grad_y, n, c, hw, gamma, save_mean, save_rstd, (T*)grad_x, dgamma, dbeta, ws, st);
+  });
 }
 
 int dhd_bn_nhwc_supported(int dtype, long rows, int c) { return bn_cl_shape_ok(dtype, rows, c) ? 1 : 0; }
@@ -634,11 +562,11 @@ int dhd_bn_nhwc_train_forward(const void* x, const void* residual, int dtype, lo
   if (!bn_cl_shape_ok(dtype, rows, c)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);
-  switch (dtype) {
-    case 0: return bn_cl_forward_t<float>((const float*)x, (const float*)residual, rows, c, flags, gamma, beta, running_mean, running_var, factor, eps, (float*)y, save_mean, save_rstd, save_affine, ws, st);
-    case 1: return bn_cl_forward_t<__half>((const __half*)x, (const __half*)residual, rows, c, flags, gamma, beta, running_mean, running_var, factor, eps, (__half*)y, save_mean, save_rstd, save_affine, ws, st);
-    default: return bn_cl_forward_t<__hip_bfloat16>((const __hip_bfloat16*)x, (const __hip_bfloat16*)residual, rows, c, flags, gamma, beta, running_mean, running_var, factor, eps, (__hip_bfloat16*)y, save_mean, save_rstd, save_affine, ws, st);
-  }
+  return dhd::with_dtype<dhd::HipHalf>(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return bn_cl_forward_t<T>((const T*)x, (const T*)residual, rows, c, flags, gamma, beta, running_mean, running_var, factor, eps, (T*)y, save_mean,
+                              save_rstd, save_affine, ws, st);
+  });
 }
 
 int dhd_bn_nhwc_train_backward(const void* x, const void* y, const void* grad_y, int dtype, long rows, int c, int flags,
@@ -650,11 +578,11 @@ int dhd_bn_nhwc_train_backward(const void* x, const void* y, const void* grad_y,
   if (!bn_cl_shape_ok(dtype, rows, c)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);
-  switch (dtype) {
-    case 0: return bn_cl_backward_t<float>((const float*)x, (const float*)y, (const float*)grad_y, rows, c, flags, gamma, save_mean, save_rstd, save_affine, (float*)grad_x, (float*)grad_residual, dgamma, dbeta, ws, st);
-    case 1: return bn_cl_backward_t<__half>((const __half*)x, (const __half*)y, (const __half*)grad_y, rows, c, flags, gamma, save_mean, save_rstd, save_affine, (__half*)grad_x, (__half*)grad_residual, dgamma, dbeta, ws, st);
-    default: return bn_cl_backward_t<__hip_bfloat16>((const __hip_bfloat16*)x, (const __hip_bfloat16*)y, (const __hip_bfloat16*)grad_y, rows, c, flags, gamma, save_mean, save_rstd, save_affine, (__hip_bfloat16*)grad_x, (__hip_bfloat16*)grad_residual, dgamma, dbeta, ws, st);
-  }
+  return dhd::with_dtype<dhd::HipHalf>(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return bn_cl_backward_t<T>((const T*)x, (const T*)y, (const T*)grad_y, rows, c, flags, gamma, save_mean, save_rstd, save_affine, (T*)grad_x,
+                               (T*)grad_residual, dgamma, dbeta, ws, st);
+  });
 }
 
 }  // extern "C"

@@ -215,7 +215,7 @@ __global__ __launch_bounds__(kBlock) void bev_pool_v2_bwd_fast_kernel(int c, int
 // longer than kChunk * L points is not walked by its own L lanes: after the short ones the whole wave takes it, every
 // group a quarter of each 64-point batch, and the groups' partial sums are added in a fixed order (deterministic).
 // ---------------------------------------------------------------------------------------------------------------
-using pf4 = __attribute__((ext_vector_type(4))) float;
+using dhd::f32x4;
 
 constexpr int kChunk = 4;   // batches of L points whose index words are in flight together
 
@@ -270,8 +270,8 @@ __device__ __forceinline__ void static_for(F&& f) {
 // dv[b]; rows k >= cnt[b] do not exist (cnt is uniform within the group, dv is 0 there).  The rows are requested before
 // the depth values are looked at: depth[] (asked for by the caller right before) and the rows travel together.
 template <int L, int R>
-__device__ __forceinline__ pf4 fwd_chunk(pf4 acc, const int (&rf)[kChunk], const float (&dv)[kChunk], const int (&cnt)[kChunk],
-                                         const pf4* __restrict__ feat, int grp, int cl) {
+__device__ __forceinline__ f32x4 fwd_chunk(f32x4 acc, const int (&rf)[kChunk], const float (&dv)[kChunk], const int (&cnt)[kChunk],
+                                         const f32x4* __restrict__ feat, int grp, int cl) {
   constexpr int U = L < R ? L : R;
 #pragma unroll
   for (int b = 0; b < kChunk; ++b) {
@@ -280,12 +280,12 @@ __device__ __forceinline__ pf4 fwd_chunk(pf4 acc, const int (&rf)[kChunk], const
     static_for<L / U>([&](auto ks) {
       constexpr int k0 = decltype(ks)::value * U;
       if (done || (k0 > 0 && !__any(cnt[b] > k0))) { done = true; return; }
-      pf4 f[U];
+      f32x4 f[U];
       float d[U];
       static_for<U>([&](auto us) {
         constexpr int u = decltype(us)::value;
         const int q = group_lane_i<L, k0 + u>(rf[b], grp);
-        f[u] = k0 + u < cnt[b] ? feat[(size_t)q * L + cl] : pf4{0.f, 0.f, 0.f, 0.f};
+        f[u] = k0 + u < cnt[b] ? feat[(size_t)q * L + cl] : f32x4{0.f, 0.f, 0.f, 0.f};
       });
       __builtin_amdgcn_sched_barrier(0);
       static_for<U>([&](auto us) {
@@ -303,11 +303,11 @@ __device__ __forceinline__ pf4 fwd_chunk(pf4 acc, const int (&rf)[kChunk], const
 // segment writer / reader, row_of = nzoff) instead of v itself.
 template <int L, int R, int WPS, bool MAPPED = false>
 __global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_fwd_vec_kernel(int n_intervals, const float* __restrict__ depth,
-                                                                      const pf4* __restrict__ feat, const int* __restrict__ ranks_depth,
+                                                                      const f32x4* __restrict__ feat, const int* __restrict__ ranks_depth,
                                                                       const int* __restrict__ ranks_feat,
                                                                       const int* __restrict__ ranks_bev,
                                                                       const int* __restrict__ interval_starts,
-                                                                      const int* __restrict__ interval_lengths, pf4* __restrict__ out,
+                                                                      const int* __restrict__ interval_lengths, f32x4* __restrict__ out,
                                                                       const int* __restrict__ row_of = nullptr, int n_rows = 0) {
   constexpr int G = DHD_WAVE / L;
   const int lane = threadIdx.x & 63, grp = lane / L, cl = lane % L;
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_fwd_vec_kernel(int n_
   }
   const bool is_long = G > 1 && len > kChunk * L && keep;
   const int own = (is_long || !keep) ? 0 : len;    // points this group walks by itself
-  pf4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int s0 = 0; __any(s0 < own); s0 += kChunk * L) {
     int rf[kChunk], rd[kChunk], cnt[kChunk];
     float dv[kChunk];
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_fwd_vec_kernel(int n_
       todo &= todo - 1;
       const int s = __builtin_amdgcn_readlane(start, src), n = __builtin_amdgcn_readlane(len, src);
       const int v = __builtin_amdgcn_readlane(vox, src);
-      pf4 part = {0.f, 0.f, 0.f, 0.f};
+      f32x4 part = {0.f, 0.f, 0.f, 0.f};
       for (int s0 = 0; s0 < n; s0 += kChunk * DHD_WAVE) {
         int rf[kChunk], rd[kChunk], cnt[kChunk];
         float dv[kChunk];
@@ -387,14 +387,14 @@ __global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_fwd_vec_kernel(int n_
 }
 
 template <int L, int R, int WPS, bool MAPPED = false>
-__global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_bwd_vec_kernel(int n_intervals, const pf4* __restrict__ out_grad,
-                                                                      const float* __restrict__ depth, const pf4* __restrict__ feat,
+__global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_bwd_vec_kernel(int n_intervals, const f32x4* __restrict__ out_grad,
+                                                                      const float* __restrict__ depth, const f32x4* __restrict__ feat,
                                                                       const int* __restrict__ ranks_depth,
                                                                       const int* __restrict__ ranks_feat,
                                                                       const int* __restrict__ ranks_bev,
                                                                       const int* __restrict__ interval_starts,
                                                                       const int* __restrict__ interval_lengths,
-                                                                      float* __restrict__ depth_grad, pf4* __restrict__ feat_grad,
+                                                                      float* __restrict__ depth_grad, f32x4* __restrict__ feat_grad,
                                                                       const int* __restrict__ row_of = nullptr, int n_rows = 0) {
   constexpr int G = DHD_WAVE / L;
   const int lane = threadIdx.x & 63, grp = lane / L, cl = lane % L;
@@ -404,8 +404,8 @@ __global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_bwd_vec_kernel(int n_
   const bool valid = len > 0;                      // empty intervals (and the padding of the last wave) write nothing
   const int start = valid ? interval_starts[iv] : 0;
   const int pix = valid ? ranks_feat[start] : 0;   // every point of the interval shares the pixel (bev_pool.py:47-57)
-  const pf4 fv = valid ? feat[(size_t)pix * L + cl] : pf4{0.f, 0.f, 0.f, 0.f};
-  pf4 facc = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 fv = valid ? feat[(size_t)pix * L + cl] : f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 facc = {0.f, 0.f, 0.f, 0.f};
   // a pixel's points (<= D per grid slice: 44 or 88) in chunks of kChunk batches whose index words and depth values are
   // requested together (round 2: per batch of L points, i.e. three dependent round trips per batch)
   for (int s0 = 0; __any(s0 < len); s0 += kChunk * L) {
@@ -439,12 +439,12 @@ __global__ __launch_bounds__(kBlock, WPS) void bev_pool_v2_bwd_vec_kernel(int n_
       static_for<L / U>([&](auto ks) {
         constexpr int k0 = decltype(ks)::value * U;
         if (done || (k0 > 0 && !__any(cnt[b] > k0))) { done = true; return; }
-        pf4 g[U];
+        f32x4 g[U];
         float d[U];
         static_for<U>([&](auto us) {
           constexpr int u = decltype(us)::value;
           const int vox = group_lane_i<L, k0 + u>(rb[b], grp);
-          g[u] = k0 + u < cnt[b] ? out_grad[(size_t)vox * L + cl] : pf4{0.f, 0.f, 0.f, 0.f};
+          g[u] = k0 + u < cnt[b] ? out_grad[(size_t)vox * L + cl] : f32x4{0.f, 0.f, 0.f, 0.f};
         });
         __builtin_amdgcn_sched_barrier(0);
         static_for<U>([&](auto us) {
@@ -658,8 +658,8 @@ int dhd_bev_pool_v2_fused_forward(const float* depth, const float* feat, float* 
   if (n_intervals > 0) {
     constexpr int LL = dhd::kTileC / 4;
     hipLaunchKernelGGL((bev_pool_v2_fwd_vec_kernel<LL, 8, 6, true>), dim3(xcd_padded_blocks(dhd_cdiv(n_intervals, kWaves * (DHD_WAVE / LL)))),
-                       dim3(kBlock), 0, st, n_intervals, depth, reinterpret_cast<const pf4*>(feat), ranks_depth, ranks_feat, ranks_bev,
-                       interval_starts, interval_lengths, reinterpret_cast<pf4*>(L.vsum), L.nzoff, L.V);
+                       dim3(kBlock), 0, st, n_intervals, depth, reinterpret_cast<const f32x4*>(feat), ranks_depth, ranks_feat, ranks_bev,
+                       interval_starts, interval_lengths, reinterpret_cast<f32x4*>(L.vsum), L.nzoff, L.V);
     DHD_LAUNCH_CHECK();
   }
   dhd::OutPtrs o;
@@ -690,9 +690,9 @@ int dhd_bev_pool_v2_fused_backward(const float* out_grad, float* depth_grad, flo
   if ((rc = dhd::launch_stream_bwd(L, in, kFusedSplit, st, true))) return rc;
   constexpr int LL = dhd::kTileC / 4;
   hipLaunchKernelGGL((bev_pool_v2_bwd_vec_kernel<LL, 8, 5, true>), dim3(xcd_padded_blocks(dhd_cdiv(n_intervals_bp, kWaves * (DHD_WAVE / LL)))),
-                     dim3(kBlock), 0, st, n_intervals_bp, reinterpret_cast<const pf4*>(L.vsum), depth, reinterpret_cast<const pf4*>(feat),
+                     dim3(kBlock), 0, st, n_intervals_bp, reinterpret_cast<const f32x4*>(L.vsum), depth, reinterpret_cast<const f32x4*>(feat),
                      ranks_depth, ranks_feat, ranks_bev, interval_starts_bp, interval_lengths_bp, depth_grad,
-                     reinterpret_cast<pf4*>(feat_grad), L.nzoff, L.V);
+                     reinterpret_cast<f32x4*>(feat_grad), L.nzoff, L.V);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -709,8 +709,8 @@ int dhd_bev_pool_v2_forward(const float* depth, const float* feat, float* out, c
 #define DHD_FWD_VEC(LL) DHD_FWD_VEC_R(LL, 8, 6)
 #define DHD_FWD_VEC_R(LL, RR, WW)                                                                                                       \
   hipLaunchKernelGGL((bev_pool_v2_fwd_vec_kernel<LL, RR, WW>), dim3(xcd_padded_blocks(dhd_cdiv(n_intervals, kWaves * (DHD_WAVE / LL)))), dim3(kBlock), 0, \
-                     dhd_stream(stream), n_intervals, depth, reinterpret_cast<const pf4*>(feat), ranks_depth, ranks_feat,    \
-                     ranks_bev, interval_starts, interval_lengths, reinterpret_cast<pf4*>(out))
+                     dhd_stream(stream), n_intervals, depth, reinterpret_cast<const f32x4*>(feat), ranks_depth, ranks_feat,    \
+                     ranks_bev, interval_starts, interval_lengths, reinterpret_cast<f32x4*>(out))
   switch (lv) {
     case 1: DHD_FWD_VEC(1); break;
     case 2: DHD_FWD_VEC(2); break;
@@ -784,9 +784,9 @@ int dhd_bev_pool_v2_backward(const float* out_grad, float* depth_grad, float* fe
 #define DHD_BWD_VEC(LL) DHD_BWD_VEC_R(LL, 8, 5)
 #define DHD_BWD_VEC_R(LL, RR, WW)                                                                                                       \
   hipLaunchKernelGGL((bev_pool_v2_bwd_vec_kernel<LL, RR, WW>), dim3(xcd_padded_blocks(dhd_cdiv(n_intervals_bp, kWaves * (DHD_WAVE / LL)))), dim3(kBlock), 0, \
-                     dhd_stream(stream), n_intervals_bp, reinterpret_cast<const pf4*>(out_grad), depth,                          \
-                     reinterpret_cast<const pf4*>(feat), ranks_depth, ranks_feat, ranks_bev, interval_starts_bp,                 \
-                     interval_lengths_bp, depth_grad, reinterpret_cast<pf4*>(feat_grad))
+                     dhd_stream(stream), n_intervals_bp, reinterpret_cast<const f32x4*>(out_grad), depth,                          \
+                     reinterpret_cast<const f32x4*>(feat), ranks_depth, ranks_feat, ranks_bev, interval_starts_bp,                 \
+                     interval_lengths_bp, depth_grad, reinterpret_cast<f32x4*>(feat_grad))
   switch (lv) {
     case 1: DHD_BWD_VEC(1); break;
     case 2: DHD_BWD_VEC(2); break;

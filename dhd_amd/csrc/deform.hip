@@ -20,13 +20,12 @@
 // im2col emits half and the two backward kernels read the half gradient (155 MB -> 78 MB per pass at the DHD-S size, and
 // no cast kernels in between); x is read, and its gradient written, as float32 or in the column type; the offsets and their
 // gradient are float32, arithmetic is float32.
-#include "common.h"
+#include "vec16.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 
-typedef __bf16 bf16_t;
 // element (image, channel, cell) of x / dx (dense NCHW: lanes = consecutive cells, so the corner gathers of a wave stay within a
 // few lines per channel plane; a channels_last x measured 5-7x slower in these kernels and is converted by the caller instead)
 __device__ __forceinline__ size_t x_at(int b, int ch, int i, int c, int hw) { return ((size_t)b * c + ch) * hw + i; }
@@ -163,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void deform_col2im_gather(const TC* __restr
   const int n = nc * khw;
   if (vec_ok) {
     constexpr int PER = 16 / (int)sizeof(TC);
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    using dhd::u32x4;
     const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
     u32x4* t4 = reinterpret_cast<u32x4*>(tile);
     for (int i = threadIdx.x; i < n / PER; i += kBlock) t4[i] = __builtin_nontemporal_load(s4 + i);   // read once
@@ -268,17 +267,16 @@ static void launch_gather(const TC* dcol, const int* starts, const uint2* entrie
   if (nc > c) nc = c >= 4 ? 4 : c >= 2 ? 2 : 1;
   const dim3 grid(dhd_cdiv(c, nc), b);
   const size_t lds = (size_t)nc * row;
-#define DHD_GATHER(NC)                                                                                                        \
-  do {                                                                                                                        \
-    if (lds > 48 * 1024)                                                                                                      \
-      (void)hipFuncSetAttribute((const void*)deform_col2im_gather<TC, NC, TX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((deform_col2im_gather<TC, NC, TX>), grid, dim3(kBlock), lds, st, dcol, starts, entries, dx, c, hw, kk, vec_ok); \
-  } while (0)
-  if (nc == 8) DHD_GATHER(8);
-  else if (nc == 4) DHD_GATHER(4);
-  else if (nc == 2) DHD_GATHER(2);
-  else DHD_GATHER(1);
-#undef DHD_GATHER
+  auto launch = [&](auto nc_tag) {
+    constexpr int NC = decltype(nc_tag)::value;
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)deform_col2im_gather<TC, NC, TX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((deform_col2im_gather<TC, NC, TX>), grid, dim3(kBlock), lds, st, dcol, starts, entries, dx, c, hw, kk, vec_ok);
+  };
+  if (nc == 8) launch(std::integral_constant<int, 8>{});
+  else if (nc == 4) launch(std::integral_constant<int, 4>{});
+  else if (nc == 2) launch(std::integral_constant<int, 2>{});
+  else launch(std::integral_constant<int, 1>{});
 }
 
 // x may be float32 (any col_dtype) or of the column type itself; dense NCHW
@@ -313,11 +311,12 @@ int dhd_deform_im2col_t(const void* x, int x_dtype, const float* offset, void* c
   const int c_chunk = c >= 32 ? 32 : c;
   const dim3 grid(dhd_cdiv((long)k * k * h * w, kBlock), dhd_cdiv(c, c_chunk), b);
   hipStream_t st = dhd_stream(stream);
-  if (col_dtype == DHD_F32) launch_im2col<float, float>(x, offset, col, grid, st, c, h, w, k, pad, dil, c_chunk);
-  else if (col_dtype == DHD_F16 && x_dtype == DHD_F32) launch_im2col<_Float16, float>(x, offset, col, grid, st, c, h, w, k, pad, dil, c_chunk);
-  else if (col_dtype == DHD_F16) launch_im2col<_Float16, _Float16>(x, offset, col, grid, st, c, h, w, k, pad, dil, c_chunk);
-  else if (x_dtype == DHD_F32) launch_im2col<bf16_t, float>(x, offset, col, grid, st, c, h, w, k, pad, dil, c_chunk);
-  else launch_im2col<bf16_t, bf16_t>(x, offset, col, grid, st, c, h, w, k, pad, dil, c_chunk);
+  dhd::with_dtype<dhd::NativeHalf>(col_dtype, [&](auto* tc) {   // the image is float32 or of the column type
+    using TC = std::remove_pointer_t<decltype(tc)>;
+    if (x_dtype == DHD_F32) launch_im2col<TC, float>(x, offset, col, grid, st, c, h, w, k, pad, dil, c_chunk);
+    else launch_im2col<TC, TC>(x, offset, col, grid, st, c, h, w, k, pad, dil, c_chunk);
+    return DHD_OK;
+  });
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -351,11 +350,12 @@ int dhd_deform_col2im_t(const void* dcol, int col_dtype, const void* x, int x_dt
   hipStream_t st = dhd_stream(stream);
   hipLaunchKernelGGL(deform_tap_sort, dim3(b), dim3(kSortBlock), (2 * (size_t)h * w + kSortBlock) * sizeof(int), st, offset, starts, entries,
                      h, w, k, pad, dil);
-  if (col_dtype == DHD_F32) launch_col2im<float, float>(dcol, x, offset, dx, doffset, starts, entries, b, c, h, w, k, pad, dil, st);
-  else if (col_dtype == DHD_F16 && x_dtype == DHD_F32) launch_col2im<_Float16, float>(dcol, x, offset, dx, doffset, starts, entries, b, c, h, w, k, pad, dil, st);
-  else if (col_dtype == DHD_F16) launch_col2im<_Float16, _Float16>(dcol, x, offset, dx, doffset, starts, entries, b, c, h, w, k, pad, dil, st);
-  else if (x_dtype == DHD_F32) launch_col2im<bf16_t, float>(dcol, x, offset, dx, doffset, starts, entries, b, c, h, w, k, pad, dil, st);
-  else launch_col2im<bf16_t, bf16_t>(dcol, x, offset, dx, doffset, starts, entries, b, c, h, w, k, pad, dil, st);
+  dhd::with_dtype<dhd::NativeHalf>(col_dtype, [&](auto* tc) {
+    using TC = std::remove_pointer_t<decltype(tc)>;
+    if (x_dtype == DHD_F32) launch_col2im<TC, float>(dcol, x, offset, dx, doffset, starts, entries, b, c, h, w, k, pad, dil, st);
+    else launch_col2im<TC, TC>(dcol, x, offset, dx, doffset, starts, entries, b, c, h, w, k, pad, dil, st);
+    return DHD_OK;
+  });
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -394,7 +394,7 @@ int dhd_deform_col2im(const float* dcol, const float* x, const float* offset, fl
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-using f32x4_t = __attribute__((ext_vector_type(4))) float;
+using dhd::f32x4;
 constexpr int kCvMaxD = 256;
 
 // softmax over the hypotheses of -cost (hypothesis d in lane d % 64, register d / 64); registers without a hypothesis hold +3e38
@@ -454,7 +454,7 @@ __device__ __forceinline__ CellRegs lane_cell(const float* __restrict__ gp, int 
   return r;
 }
 
-__device__ __forceinline__ float pick(const f32x4_t& v, int comp) {
+__device__ __forceinline__ float pick(const f32x4& v, int comp) {
   return comp == 0 ? v.x : comp == 1 ? v.y : comp == 2 ? v.z : v.w;
 }
 
@@ -470,23 +470,23 @@ __global__ __launch_bounds__(kBlock) void stereo_cost_volume_kernel(const float*
   const int bn = pix / hw, yx = pix % hw;
   const int c4 = c >> 2;                       // float4 groups per pixel
   const float* pb = prev + (size_t)bn * hw * c;
-  f32x4_t cur[Q];
+  f32x4 cur[Q];
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
     const int g = lane + 64 * q;
-    cur[q] = g < c4 ? reinterpret_cast<const f32x4_t*>(curr + (size_t)pix * c)[g] : f32x4_t{0.f, 0.f, 0.f, 0.f};
+    cur[q] = g < c4 ? reinterpret_cast<const f32x4*>(curr + (size_t)pix * c)[g] : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const int flag_group = flag_channel >> 2, flag_comp = flag_channel & 3;
   float mine[kCvMaxD / DHD_WAVE];  // cost of hypothesis d lives in lane d % 64, register d / 64
 #pragma unroll
   for (int q = 0; q < kCvMaxD / DHD_WAVE; ++q) mine[q] = 3.0e38f;
   const float* gp = grid + ((size_t)bn * nd * hw + yx) * 2;
-  f32x4_t cache[4][Q];
+  f32x4 cache[4][Q];
   int cidx[4] = {-1, -1, -1, -1};
 #pragma unroll
   for (int k = 0; k < 4; ++k)
 #pragma unroll
-    for (int q = 0; q < Q; ++q) cache[k][q] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < Q; ++q) cache[k][q] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int d0 = 0; d0 < nd; d0 += DHD_WAVE) {
     const CellRegs cell = lane_cell(gp, d0 + lane, nd, hw, h, w);
     const int nb = min(DHD_WAVE, nd - d0);
@@ -499,13 +499,13 @@ __global__ __launch_bounds__(kBlock) void stereo_cost_volume_kernel(const float*
         wt[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cell.wt[k]), i));
       }
       if (nidx[0] != cidx[0] || nidx[1] != cidx[1] || nidx[2] != cidx[2] || nidx[3] != cidx[3]) {
-        f32x4_t nv[4][Q];
+        f32x4 nv[4][Q];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int want = nidx[k];
           if (want < 0) {
 #pragma unroll
-            for (int q = 0; q < Q; ++q) nv[k][q] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < Q; ++q) nv[k][q] = f32x4{0.f, 0.f, 0.f, 0.f};
           } else if (want == cidx[0]) {
 #pragma unroll
             for (int q = 0; q < Q; ++q) nv[k][q] = cache[0][q];
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(kBlock) void stereo_cost_volume_kernel(const float*
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
               const int g = lane + 64 * q;
-              nv[k][q] = g < c4 ? reinterpret_cast<const f32x4_t*>(pb + (size_t)want * c)[g] : f32x4_t{0.f, 0.f, 0.f, 0.f};
+              nv[k][q] = g < c4 ? reinterpret_cast<const f32x4*>(pb + (size_t)want * c)[g] : f32x4{0.f, 0.f, 0.f, 0.f};
             }
           }
         }
@@ -538,11 +538,11 @@ __global__ __launch_bounds__(kBlock) void stereo_cost_volume_kernel(const float*
       for (int q = 0; q < Q; ++q) {
         const int g = lane + 64 * q;
         if (g >= c4) break;
-        f32x4_t s = {0.f, 0.f, 0.f, 0.f};
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < 4; ++k)
           if (cidx[k] >= 0) s += wt[k] * cache[k][q];
-        const f32x4_t df = cur[q] - s;
+        const f32x4 df = cur[q] - s;
         acc += (fabsf(df.x) + fabsf(df.y)) + (fabsf(df.z) + fabsf(df.w));
         if (g == flag_group) flag = pick(s, flag_comp);
       }
@@ -570,32 +570,32 @@ __global__ __launch_bounds__(kBlock) void stereo_cost_volume_pair_kernel(const f
   const int c4 = c >> 2;
   const bool live = g < c4;
   const float* pb = prev + (size_t)bn * hw * c + 4 * g;
-  const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
-  const f32x4_t cur = live ? reinterpret_cast<const f32x4_t*>(curr + (size_t)pix * c)[g] : zero;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 cur = live ? reinterpret_cast<const f32x4*>(curr + (size_t)pix * c)[g] : zero;
   const int flag_group = flag_channel >> 2, flag_comp = flag_channel & 3;
   float mine[kCvMaxD / DHD_WAVE];
 #pragma unroll
   for (int q = 0; q < kCvMaxD / DHD_WAVE; ++q) mine[q] = 3.0e38f;
   const float* gp = grid + ((size_t)bn * nd * hw + yx) * 2;
-  f32x4_t cache[4] = {zero, zero, zero, zero};
+  f32x4 cache[4] = {zero, zero, zero, zero};
   int cidx[4] = {-1, -1, -1, -1};
   for (int d0 = 0; d0 < nd; d0 += DHD_WAVE) {
     const CellRegs cell = lane_cell(gp, d0 + lane, nd, hw, h, w);
     const int nb = min(DHD_WAVE, nd - d0);
     for (int i = 0; i < nb; i += 2) {
       const int src = i + half;                 // the lane that holds this half's hypothesis (beyond nb: every index -1)
-      f32x4_t s = zero;
+      f32x4 s = zero;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int want = __shfl(cell.idx[k], src, DHD_WAVE);
         const float wk = __shfl(cell.wt[k], src, DHD_WAVE);
         if (want != cidx[k]) {                   // per lane: the halves walk their own lines
-          cache[k] = (want >= 0 && live) ? *reinterpret_cast<const f32x4_t*>(pb + (size_t)want * c) : zero;
+          cache[k] = (want >= 0 && live) ? *reinterpret_cast<const f32x4*>(pb + (size_t)want * c) : zero;
           cidx[k] = want;
         }
         if (want >= 0) s += wk * cache[k];
       }
-      const f32x4_t df = cur - s;
+      const f32x4 df = cur - s;
       float acc = live ? (fabsf(df.x) + fabsf(df.y)) + (fabsf(df.z) + fabsf(df.w)) : 0.f;
       // the first five steps of wave_sum_bcast: lane 31 = sum of lanes 0-31, lane 63 = sum of lanes 32-63
       acc = dpp_add<0xB1, 0xf>(acc);

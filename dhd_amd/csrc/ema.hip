@@ -2,13 +2,13 @@
 // the reference walks the state dict with two eager ops per tensor (v *= d; v += (1-d)*m), i.e.
 // ~1000 launches per training iteration for DHD-S.  Here: one launch over a chunk table that covers
 // every float32 tensor of the state, each element read and written once.
-#include "common.h"
+#include "vec16.h"
 
 namespace {
 
 constexpr int kEmaBlock = 256;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using dhd::f32x4;
 
 // The reference's arithmetic, rounding for rounding: fl(fl(v*d) + fl(omd*m)); the build has
 // -ffp-contract=off, so neither product is fused into the add.

@@ -36,22 +36,21 @@ int launch_transpose(const float* src, float* dst, int batch, int rows, int cols
 }
 
 // dhd_hbm_calibrate patterns 1 / 2: linear grid-stride sweeps with 16-byte non-temporal accesses, 4 per thread in flight
-typedef float f4 __attribute__((ext_vector_type(4)));
 constexpr int kCalBlock = 512;
 
-__global__ __launch_bounds__(kCalBlock) void hbm_fill_kernel(f4* __restrict__ buf, size_t n4) {
-  const f4 z = {0.f, 0.f, 0.f, 0.f};
+__global__ __launch_bounds__(kCalBlock) void hbm_fill_kernel(f32x4* __restrict__ buf, size_t n4) {
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   const size_t stride = (size_t)gridDim.x * kCalBlock;
   for (size_t i = (size_t)blockIdx.x * kCalBlock + threadIdx.x; i < n4; i += stride) __builtin_nontemporal_store(z, buf + i);
 }
 
-__global__ __launch_bounds__(kCalBlock) void hbm_read_kernel(f4* __restrict__ buf, size_t n4) {
+__global__ __launch_bounds__(kCalBlock) void hbm_read_kernel(f32x4* __restrict__ buf, size_t n4) {
   const size_t stride = (size_t)gridDim.x * kCalBlock;
-  f4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   size_t i = (size_t)blockIdx.x * kCalBlock + threadIdx.x;
   for (; i + 3 * stride < n4; i += 4 * stride) {
-    const f4 a = __builtin_nontemporal_load(buf + i), b = __builtin_nontemporal_load(buf + i + stride);
-    const f4 c = __builtin_nontemporal_load(buf + i + 2 * stride), d = __builtin_nontemporal_load(buf + i + 3 * stride);
+    const f32x4 a = __builtin_nontemporal_load(buf + i), b = __builtin_nontemporal_load(buf + i + stride);
+    const f32x4 c = __builtin_nontemporal_load(buf + i + 2 * stride), d = __builtin_nontemporal_load(buf + i + 3 * stride);
     acc += (a + b) + (c + d);
   }
   for (; i < n4; i += stride) acc += __builtin_nontemporal_load(buf + i);
@@ -94,10 +93,10 @@ int dhd_hbm_calibrate(void* buf, size_t bytes, int pattern, void* stream) {
   if (pattern == 0) {
     DHD_HIP(hipMemsetAsync(buf, 0, bytes, st));
   } else if (pattern == 1) {
-    hipLaunchKernelGGL(hbm_fill_kernel, dim3(blocks), dim3(kCalBlock), 0, st, static_cast<f4*>(buf), n4);
+    hipLaunchKernelGGL(hbm_fill_kernel, dim3(blocks), dim3(kCalBlock), 0, st, static_cast<f32x4*>(buf), n4);
     DHD_LAUNCH_CHECK();
   } else if (pattern == 2) {
-    hipLaunchKernelGGL(hbm_read_kernel, dim3(blocks), dim3(kCalBlock), 0, st, static_cast<f4*>(buf), n4);
+    hipLaunchKernelGGL(hbm_read_kernel, dim3(blocks), dim3(kCalBlock), 0, st, static_cast<f32x4*>(buf), n4);
     DHD_LAUNCH_CHECK();
   } else {
     return DHD_EINVAL;

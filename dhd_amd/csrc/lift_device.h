@@ -1,7 +1,7 @@
 // Device code shared by the stand-alone lift kernels (lift.hip) and the fused prologue of dhd_mghs_lift
 // (mghs_prepare.hip): height argmax -> band id, and 64 x 64 transposition tiles of the context features.
 #pragma once
-#include "common.h"
+#include "vec16.h"
 
 namespace dhd {
 
@@ -54,7 +54,6 @@ __device__ __forceinline__ void height_band_block(int block, const float* __rest
   if (ok && sub == 0) band[p] = lut.band[arg < n_height ? arg : 0];
 }
 
-typedef float lift_f4 __attribute__((ext_vector_type(4)));
 
 // One 64 x 64 tile of (batch, rows, cols) -> (batch, cols, rows) through a padded LDS tile, scalar accesses.
 __device__ __forceinline__ void transpose_tile(float (*tile)[65], const float* __restrict__ src, float* __restrict__ dst, int rows,
@@ -81,12 +80,12 @@ __device__ __forceinline__ void transpose4_tile(float (*tile)[65], const float* 
                                                 int cols, int b, int r0, int c0) {
   const float* s = src + (size_t)b * rows * cols;
   float* d = dst + (size_t)b * rows * cols;
-  lift_f4 v[4];
+  f32x4 v[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {          // tile row j, columns 4 q .. 4 q + 3
     const int idx = threadIdx.x + k * kLiftBlock, j = idx >> 4, q = idx & 15;
     const int r = r0 + j, c = c0 + 4 * q;
-    v[k] = (r < rows && c < cols) ? *reinterpret_cast<const lift_f4*>(s + (size_t)r * cols + c) : lift_f4{0.f, 0.f, 0.f, 0.f};
+    v[k] = (r < rows && c < cols) ? *reinterpret_cast<const f32x4*>(s + (size_t)r * cols + c) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -100,8 +99,8 @@ __device__ __forceinline__ void transpose4_tile(float (*tile)[65], const float* 
     const int idx = threadIdx.x + k * kLiftBlock, j = idx >> 4, q = idx & 15;
     const int c = c0 + j, r = r0 + 4 * q;
     if (c < cols && r < rows) {
-      const lift_f4 w = {tile[4 * q][j], tile[4 * q + 1][j], tile[4 * q + 2][j], tile[4 * q + 3][j]};
-      *reinterpret_cast<lift_f4*>(d + (size_t)c * rows + r) = w;
+      const f32x4 w = {tile[4 * q][j], tile[4 * q + 1][j], tile[4 * q + 2][j], tile[4 * q + 3][j]};
+      *reinterpret_cast<f32x4*>(d + (size_t)c * rows + r) = w;
     }
   }
 }

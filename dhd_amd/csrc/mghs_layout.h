@@ -1,7 +1,7 @@
 // Workspace layout and shared device helpers of the fused MGHS kernels (mghs_prepare.hip,
 // mghs_pool.hip).
 #pragma once
-#include "common.h"
+#include "vec16.h"
 
 namespace dhd {
 
@@ -195,8 +195,6 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, DHD_WAVE);
   return v;
 }
-
-typedef float vfloat4 __attribute__((ext_vector_type(4)));  // native vector: accepted by the nontemporal builtins
 
 // Where grid g's dense tensor lives: element (b, z, c, y, x) is at
 //   p[g] + b*sb[g] + z*sz[g] + c*sc[g] + y*nx + x   (floats).

@@ -228,9 +228,9 @@ constexpr int kDepthChunk = 8;
 
 __global__ __launch_bounds__(kBlock) void mghs_zero_grid0_rows(Layout L) {
   const int n0 = L.nzoff[L.vox_base[1]];                       // non-empty voxels of grid 0 = its slots [0, n0)
-  vfloat4* v = reinterpret_cast<vfloat4*>(L.vsum);
+  f32x4* v = reinterpret_cast<f32x4*>(L.vsum);
   const size_t n4 = (size_t)n0 * (kTileC / 4);
-  const vfloat4 z = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) v[i] = z;
 }
 
@@ -337,39 +337,21 @@ constexpr size_t kStreamLds = (size_t)kTableFloats * 4 + (size_t)kSegMaxVox * 2 
 // Element types of the dense tensors (dhd_tensor_view.dtype): a lane always moves 16 bytes = kVox<T> voxels of one channel run.
 // Half types: float32 sums from the table, rounded to nearest even on the way out (what `.half()` / `.bfloat16()` of the
 // float32 tensor would give); gradients are widened exactly.
-template <class T> struct VoxVec { static constexpr int n = 16 / sizeof(T); };
-template <class T> __device__ __forceinline__ vfloat4 pack_vox(const float* f);
-template <> __device__ __forceinline__ vfloat4 pack_vox<float>(const float* f) { return vfloat4{f[0], f[1], f[2], f[3]}; }
-template <> __device__ __forceinline__ vfloat4 pack_vox<_Float16>(const float* f) {
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-  const h8 v = {(_Float16)f[0], (_Float16)f[1], (_Float16)f[2], (_Float16)f[3], (_Float16)f[4], (_Float16)f[5], (_Float16)f[6], (_Float16)f[7]};
-  return __builtin_bit_cast(vfloat4, v);
-}
-template <> __device__ __forceinline__ vfloat4 pack_vox<__bf16>(const float* f) {
-  typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-  const b8 v = {(__bf16)f[0], (__bf16)f[1], (__bf16)f[2], (__bf16)f[3], (__bf16)f[4], (__bf16)f[5], (__bf16)f[6], (__bf16)f[7]};
-  return __builtin_bit_cast(vfloat4, v);
-}
-template <class T> __device__ __forceinline__ void unpack_vox(vfloat4 v, float* f);
-template <> __device__ __forceinline__ void unpack_vox<float>(vfloat4 v, float* f) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
-template <> __device__ __forceinline__ void unpack_vox<_Float16>(vfloat4 v, float* f) {
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-  const h8 h = __builtin_bit_cast(h8, v);
+// element-wise converts: the pairwise narrow16<T> gives the same instructions in another order
+template <class T> __device__ __forceinline__ f32x4 pack_vox(const float* f) {
+  typedef T vox __attribute__((ext_vector_type(kVec16<T>)));
+  vox v;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) f[k] = (float)h[k];
+  for (int k = 0; k < kVec16<T>; ++k) v[k] = (T)f[k];
+  return __builtin_bit_cast(f32x4, v);
 }
-template <> __device__ __forceinline__ void unpack_vox<__bf16>(vfloat4 v, float* f) {
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  const u4 w = __builtin_bit_cast(u4, v);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { f[2 * k] = __uint_as_float(w[k] << 16); f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u); }
-}
+template <class T> __device__ __forceinline__ void unpack_vox(f32x4 v, float* f) { widen16<T>(__builtin_bit_cast(raw16<T>, v), f); }
 
 // OP = 1: the same code instantiated once more for the single-grid operator (dhd_bev_pool_v2_fused_*), so that its launches are
 // their own rows in a kernel profile instead of being averaged into the hot path's.
 template <class T, int OP = 0>
 __global__ __launch_bounds__(kStreamBlock) void mghs_stream_fwd(Layout L, OutPtrs out, int split) {
-  constexpr int VPL = VoxVec<T>::n;                // voxels per lane and store: 4 (float32) or 8 (half types)
+  constexpr int VPL = kVec16<T>;                // voxels per lane and store: 4 (float32) or 8 (half types)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* table = reinterpret_cast<float*>(smem);
   unsigned short* slot_of = reinterpret_cast<unsigned short*>(smem + (size_t)kTableFloats * 4);
@@ -431,7 +413,7 @@ __global__ __launch_bounds__(kStreamBlock) void mghs_stream_fwd(Layout L, OutPtr
           if (s1) f[2 * k + 1] = table[cc * pitch + (s1 - 1)];
         }
       }
-      vfloat4* dst = reinterpret_cast<vfloat4*>(base + (size_t)cc * sc) + i;
+      f32x4* dst = reinterpret_cast<f32x4*>(base + (size_t)cc * sc) + i;
       // streamed once, not re-read here: non-temporal, so the output stream does not evict vsum from L2
       __builtin_nontemporal_store(pack_vox<T>(f), dst);
       cc += q_step;
@@ -447,7 +429,7 @@ __global__ __launch_bounds__(kStreamBlock) void mghs_stream_fwd(Layout L, OutPtr
 // ---------------------------------------------------------------------------------------
 template <class T, int OP = 0>
 __global__ __launch_bounds__(kStreamBlock) void mghs_stream_bwd(Layout L, InPtrs og_in, int split) {
-  constexpr int VPL = VoxVec<T>::n;
+  constexpr int VPL = kVec16<T>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* table = reinterpret_cast<float*>(smem);
   unsigned short* slot_of = reinterpret_cast<unsigned short*>(smem + (size_t)kTableFloats * 4);
@@ -489,7 +471,7 @@ __global__ __launch_bounds__(kStreamBlock) void mghs_stream_bwd(Layout L, InPtrs
     int cc = idx / nvec, i = idx % nvec;
     for (; idx - lane < total; ) {                 // wave-uniform condition
       unsigned sl[kBatch][VPL / 2], any[kBatch];
-      vfloat4 v[kBatch];
+      f32x4 v[kBatch];
       int ccs[kBatch];
 #pragma unroll
       for (int k = 0; k < kBatch; ++k) {
@@ -505,8 +487,8 @@ __global__ __launch_bounds__(kStreamBlock) void mghs_stream_bwd(Layout L, InPtrs
 #pragma unroll
         for (int u = 0; u < VPL / 2; ++u) any[k] |= sl[k][u];
         ccs[k] = cc;
-        const vfloat4* p = any[k] ? reinterpret_cast<const vfloat4*>(gbase + (size_t)(c_lo + cc) * sc) + i
-                                  : reinterpret_cast<const vfloat4*>(L.vsum);
+        const f32x4* p = any[k] ? reinterpret_cast<const f32x4*>(gbase + (size_t)(c_lo + cc) * sc) + i
+                                  : reinterpret_cast<const f32x4*>(L.vsum);
         v[k] = __builtin_nontemporal_load(p);
         idx += kStride;
         cc += q_step;
@@ -570,9 +552,9 @@ __global__ __launch_bounds__(kBlock) void mghs_pixel_bwd(Layout L, const float* 
   if (q >= L.B * L.N * L.hw) return;
   const int bn = q / L.hw, pl = q % L.hw;
   const int p0 = bn * L.dhw + pl;  // point id of depth bin 0; bin d is p0 + d*hw
-  const vfloat4 f = reinterpret_cast<const vfloat4*>(feat)[(size_t)q * (kTileC / 4) + cq];
-  const vfloat4* gc = reinterpret_cast<const vfloat4*>(L.vsum) + cq;
-  vfloat4 fg = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 f = reinterpret_cast<const f32x4*>(feat)[(size_t)q * (kTileC / 4) + cq];
+  const f32x4* gc = reinterpret_cast<const f32x4*>(L.vsum) + cq;
+  f32x4 fg = {0.f, 0.f, 0.f, 0.f};
   // 2*D (depth bin, grid class) candidates, 64 at a time: lane c loads the slot / depth of candidate e0 + c = (bin, class)
   const int n_cand = 2 * L.D;
   constexpr int kRounds = DHD_WAVE / 4, kU = 8;   // 16 rounds of 4 candidates, 8 rounds (32 rows) in flight
@@ -590,7 +572,7 @@ __global__ __launch_bounds__(kBlock) void mghs_pixel_bwd(Layout L, const float* 
 #pragma unroll
     for (int u0 = 0; u0 < kRounds; u0 += kU) {
       if (4 * u0 >= nb) break;  // wave-uniform
-      vfloat4 g[kU];
+      f32x4 g[kU];
       float d[kU];
 #pragma unroll
       for (int j = 0; j < kU; ++j) {
@@ -628,7 +610,7 @@ __global__ __launch_bounds__(kBlock) void mghs_pixel_bwd(Layout L, const float* 
 #pragma unroll
       for (int c = 0; c < 4; ++c) dst[(size_t)c * L.hw] = fg[c];
     } else {
-      reinterpret_cast<vfloat4*>(feat_grad)[(size_t)q * (kTileC / 4) + cq] = fg;
+      reinterpret_cast<f32x4*>(feat_grad)[(size_t)q * (kTileC / 4) + cq] = fg;
     }
   }
 }
@@ -754,9 +736,9 @@ __global__ __launch_bounds__(kRowBlock) void mghs_rows_fwd(Layout L, const float
     size_t row = (size_t)rt.b * out.sb[rt.g] + (size_t)rt.z * out.sz[rt.g] + (size_t)(c0 + cc) * out.sc[rt.g] + (size_t)rt.y * rt.nx + x0;
     const float* src = tile + cc * tile_stride;
     if (vec) {
-      vfloat4* dst = reinterpret_cast<vfloat4*>(og + row);
+      f32x4* dst = reinterpret_cast<f32x4*>(og + row);
       for (int i = lane; i < xn / 4; i += DHD_WAVE) {
-        vfloat4 v = {src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]};
+        f32x4 v = {src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]};
         __builtin_nontemporal_store(v, dst + i);
       }
     } else {
@@ -871,11 +853,11 @@ int launch_stream_fwd(const Layout& L, const OutPtrs& o, int split, hipStream_t 
     DHD_LAUNCH_CHECK();
     return DHD_OK;
   }
-  if (o.dtype == DHD_F16) hipLaunchKernelGGL(mghs_stream_fwd<_Float16>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split);
-  else if (o.dtype == DHD_BF16) hipLaunchKernelGGL(mghs_stream_fwd<__bf16>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split);
-  else hipLaunchKernelGGL(mghs_stream_fwd<float>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split);
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
+  return with_dtype<NativeHalf>(o.dtype, [&](auto* t) {
+    hipLaunchKernelGGL(mghs_stream_fwd<std::remove_pointer_t<decltype(t)>>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split);
+    DHD_LAUNCH_CHECK();
+    return DHD_OK;
+  });
 }
 
 int launch_stream_bwd(const Layout& L, const InPtrs& in, int split, hipStream_t st, bool op) {
@@ -886,11 +868,11 @@ int launch_stream_bwd(const Layout& L, const InPtrs& in, int split, hipStream_t 
     DHD_LAUNCH_CHECK();
     return DHD_OK;
   }
-  if (in.dtype == DHD_F16) hipLaunchKernelGGL(mghs_stream_bwd<_Float16>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, in, split);
-  else if (in.dtype == DHD_BF16) hipLaunchKernelGGL(mghs_stream_bwd<__bf16>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, in, split);
-  else hipLaunchKernelGGL(mghs_stream_bwd<float>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, in, split);
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
+  return with_dtype<NativeHalf>(in.dtype, [&](auto* t) {
+    hipLaunchKernelGGL(mghs_stream_bwd<std::remove_pointer_t<decltype(t)>>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, in, split);
+    DHD_LAUNCH_CHECK();
+    return DHD_OK;
+  });
 }
 
 }  // namespace dhd

@@ -25,7 +25,6 @@ namespace {
 using namespace dhd;
 
 constexpr int kBlock = 256;
-typedef __bf16 bf16_t;
 
 // element (image, channel, pixel) of a (BN, CT, hw) tensor that is dense NCHW (nhwc = 0) or channels_last (nhwc = 1)
 struct View {
@@ -139,30 +138,6 @@ __global__ __launch_bounds__(kBlock) void dh_softmax_bwd(const float* __restrict
   st(gxd, vx.at(bn, d + ch, p), v);
 }
 
-template <typename TX>
-int fwd_h(int hl_dtype, dim3 grid, hipStream_t stq, const TX* xd, View vx, const void* hl, View vh, int bn, int d, int c, int hb,
-          const BandLut& lut, float* depth, float* feat, float* height, uint8_t* band, int nb_pix) {
-#define DHD_FWD(TH) hipLaunchKernelGGL((dh_softmax_fwd<TX, TH>), grid, dim3(kBlock), 0, stq, xd, vx, (const TH*)hl, vh, bn, d, c, hb, lut, depth, feat, height, band, nb_pix)
-  if (hl_dtype == DHD_F32) DHD_FWD(float);
-  else if (hl_dtype == DHD_F16) DHD_FWD(_Float16);
-  else if (hl_dtype == DHD_BF16) DHD_FWD(bf16_t);
-  else return DHD_EINVAL;
-#undef DHD_FWD
-  return DHD_OK;
-}
-
-template <typename TX>
-int bwd_h(int hl_dtype, dim3 grid, hipStream_t stq, const float* gd, const float* gf, const float* gh, const float* depth, const float* height,
-          int bn, int d, int c, int hb, TX* gxd, View vx, void* ghl, View vh, int nb_pix) {
-#define DHD_BWD(TH) hipLaunchKernelGGL((dh_softmax_bwd<TX, TH>), grid, dim3(kBlock), 0, stq, gd, gf, gh, depth, height, bn, d, c, hb, gxd, vx, (TH*)ghl, vh, nb_pix)
-  if (hl_dtype == DHD_F32) DHD_BWD(float);
-  else if (hl_dtype == DHD_F16) DHD_BWD(_Float16);
-  else if (hl_dtype == DHD_BF16) DHD_BWD(bf16_t);
-  else return DHD_EINVAL;
-#undef DHD_BWD
-  return DHD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -181,14 +156,16 @@ int dhd_mghs_softmax_forward(const void* xd, int xd_dtype, int xd_nhwc, int ct, 
   const dim3 grid(2 * nb_pix + dhd_cdiv((long)bn * c * hw, kBlock));
   const View vx{ct, hw, xd_nhwc ? 1 : 0}, vh{ht, hw, hl_nhwc ? 1 : 0};
   hipStream_t stq = dhd_stream(stream);
-  int rc;
-  if (xd_dtype == DHD_F32) rc = fwd_h<float>(hl_dtype, grid, stq, (const float*)xd, vx, hl, vh, bn, d, c, h_bins, lut, depth, feat, height, band, nb_pix);
-  else if (xd_dtype == DHD_F16) rc = fwd_h<_Float16>(hl_dtype, grid, stq, (const _Float16*)xd, vx, hl, vh, bn, d, c, h_bins, lut, depth, feat, height, band, nb_pix);
-  else if (xd_dtype == DHD_BF16) rc = fwd_h<bf16_t>(hl_dtype, grid, stq, (const bf16_t*)xd, vx, hl, vh, bn, d, c, h_bins, lut, depth, feat, height, band, nb_pix);
-  else return DHD_EINVAL;
-  if (rc != DHD_OK) return rc;
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
+  return with_dtype<NativeHalf>(xd_dtype, [&](auto* tx) {
+    return with_dtype<NativeHalf>(hl_dtype, [&](auto* th) {
+      using TX = std::remove_pointer_t<decltype(tx)>;
+      using TH = std::remove_pointer_t<decltype(th)>;
+      hipLaunchKernelGGL((dh_softmax_fwd<TX, TH>), grid, dim3(kBlock), 0, stq, (const TX*)xd, vx, (const TH*)hl, vh, bn, d, c, h_bins, lut, depth,
+                         feat, height, band, nb_pix);
+      DHD_LAUNCH_CHECK();
+      return DHD_OK;
+    });
+  });
 }
 
 int dhd_mghs_softmax_backward(const float* g_depth, const float* g_feat, const float* g_height, const float* depth, const float* height,
@@ -202,14 +179,16 @@ int dhd_mghs_softmax_backward(const float* g_depth, const float* g_feat, const f
   const dim3 grid(2 * nb_pix + (g_xd ? dhd_cdiv((long)bn * (ct - d) * hw, kBlock) : 0));
   const View vx{ct, hw, xd_nhwc ? 1 : 0}, vh{ht, hw, hl_nhwc ? 1 : 0};
   hipStream_t stq = dhd_stream(stream);
-  int rc;
-  if (!g_xd || xd_dtype == DHD_F32) rc = bwd_h<float>(hl_dtype, grid, stq, g_depth, g_feat, g_height, depth, height, bn, d, c, h_bins, (float*)g_xd, vx, g_hl, vh, nb_pix);
-  else if (xd_dtype == DHD_F16) rc = bwd_h<_Float16>(hl_dtype, grid, stq, g_depth, g_feat, g_height, depth, height, bn, d, c, h_bins, (_Float16*)g_xd, vx, g_hl, vh, nb_pix);
-  else if (xd_dtype == DHD_BF16) rc = bwd_h<bf16_t>(hl_dtype, grid, stq, g_depth, g_feat, g_height, depth, height, bn, d, c, h_bins, (bf16_t*)g_xd, vx, g_hl, vh, nb_pix);
-  else return DHD_EINVAL;
-  if (rc != DHD_OK) return rc;
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
+  return with_dtype<NativeHalf>(g_xd ? xd_dtype : DHD_F32, [&](auto* tx) {
+    return with_dtype<NativeHalf>(hl_dtype, [&](auto* th) {
+      using TX = std::remove_pointer_t<decltype(tx)>;
+      using TH = std::remove_pointer_t<decltype(th)>;
+      hipLaunchKernelGGL((dh_softmax_bwd<TX, TH>), grid, dim3(kBlock), 0, stq, g_depth, g_feat, g_height, depth, height, bn, d, c, h_bins,
+                         (TX*)g_xd, vx, (TH*)g_hl, vh, nb_pix);
+      DHD_LAUNCH_CHECK();
+      return DHD_OK;
+    });
+  });
 }
 
 }  // extern "C"

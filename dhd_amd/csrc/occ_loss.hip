@@ -17,11 +17,11 @@
 // Traffic: 2 x 72 B read + 72 B written per voxel (+2 B labels/mask each pass); no (M,18) temporaries.
 // Logit tiles go through LDS so that global accesses are 16-byte coalesced although a voxel's 18 logits
 // are 72 contiguous bytes: a thread reads its voxel as nine conflict-free ds_read_b64.
-#include "common.h"
+#include "vec16.h"
 
 namespace {
 
-using f32x4_t = __attribute__((ext_vector_type(4))) float;
+using dhd::f32x4;
 
 constexpr int K = 18;              // classes (Occ3D-nuScenes: 17 semantic + free)
 constexpr int kBlock = 256;        // one voxel per thread per tile
@@ -62,9 +62,9 @@ __device__ __forceinline__ void softmax18(const float* row, int t, Voxel& v) {
 
 // copy tile [first voxel v0, n_in voxels) of the (M,18) matrix into LDS with 16-byte accesses
 __device__ __forceinline__ void load_tile(const float* __restrict__ logits, long v0, int n_in, float* tile) {
-  const f32x4_t* src = reinterpret_cast<const f32x4_t*>(logits + v0 * K);  // v0 is a multiple of kBlock: 16-byte aligned
+  const f32x4* src = reinterpret_cast<const f32x4*>(logits + v0 * K);  // v0 is a multiple of kBlock: 16-byte aligned
   const int n4 = (n_in * K) >> 2, rest = (n_in * K) & 3;
-  for (int i = threadIdx.x; i < n4; i += kBlock) reinterpret_cast<f32x4_t*>(tile)[i] = src[i];
+  for (int i = threadIdx.x; i < n4; i += kBlock) reinterpret_cast<f32x4*>(tile)[i] = src[i];
   if (threadIdx.x < rest) tile[4 * n4 + threadIdx.x] = logits[v0 * K + 4 * n4 + threadIdx.x];
 }
 
@@ -315,9 +315,9 @@ __global__ __launch_bounds__(kBlock) void occ_loss_grad(const float* __restrict_
     }
     __syncthreads();
     {
-      f32x4_t* dst = reinterpret_cast<f32x4_t*>(grad + v0 * K);
+      f32x4* dst = reinterpret_cast<f32x4*>(grad + v0 * K);
       const int n4 = (n_in * K) >> 2, rest = (n_in * K) & 3;
-      for (int i = threadIdx.x; i < n4; i += kBlock) __builtin_nontemporal_store(reinterpret_cast<const f32x4_t*>(tile)[i], dst + i);
+      for (int i = threadIdx.x; i < n4; i += kBlock) __builtin_nontemporal_store(reinterpret_cast<const f32x4*>(tile)[i], dst + i);
       if ((int)threadIdx.x < rest) grad[v0 * K + 4 * n4 + threadIdx.x] = tile[4 * n4 + threadIdx.x];
     }
   }

@@ -23,50 +23,24 @@
 namespace dhd_sfa {
 
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 
 template <class TS> struct HalfOps;
 template <> struct HalfOps<_Float16> {
-  static __device__ __forceinline__ f32x2 widen2(unsigned w) {
-    const f16x2 h = __builtin_bit_cast(f16x2, w);
-    return f32x2{(float)h.x, (float)h.y};
-  }
-  static __device__ __forceinline__ unsigned narrow2(f32x2 v) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-  }
   static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   }
 };
 template <> struct HalfOps<__bf16> {
-  static __device__ __forceinline__ f32x2 widen2(unsigned w) { return unpack_bf16(w); }
-  static __device__ __forceinline__ unsigned narrow2(f32x2 v) { return pack_bf16(v); }
   static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return mfma_bf16(a, b, c); }
 };
 
-// 8 consecutive elements of TS (16 bytes) <-> 8 floats (widened exactly / rounded to nearest even)
-template <class TS> __device__ __forceinline__ void widen8(u32x4 w, float* v) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2 p = HalfOps<TS>::widen2(w[i]);
-    v[2 * i] = p.x;
-    v[2 * i + 1] = p.y;
-  }
-}
-template <class TS> __device__ __forceinline__ u32x4 narrow8(const float* v) {
-  u32x4 w;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = HalfOps<TS>::narrow2(f32x2{v[2 * i], v[2 * i + 1]});
-  return w;
-}
+// vector i8 of 8 consecutive elements of TS (16 bytes) <-> 8 floats (widened exactly / rounded to nearest even), streamed
 template <class TS> __device__ __forceinline__ void ld8(const TS* base, size_t i8, float* v) {
-  widen8<TS>(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base) + i8), v);
+  widen16<TS>(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base) + i8), v);
 }
 template <class TS> __device__ __forceinline__ void st8(TS* base, size_t i8, const float* v) {
-  __builtin_nontemporal_store(narrow8<TS>(v), reinterpret_cast<u32x4*>(base) + i8);
+  __builtin_nontemporal_store(narrow16<TS>(v), reinterpret_cast<u32x4*>(base) + i8);
 }
-// the value a float becomes when it is stored as TS and read back
-template <class TS> __device__ __forceinline__ f32x2 round2(f32x2 v) { return HalfOps<TS>::widen2(HalfOps<TS>::narrow2(v)); }
 
 // ------------------------------------------------------------------------------------------------------------------------
 // pw_gemm_cuh_kernel
@@ -100,7 +74,7 @@ __device__ __forceinline__ void cuh_pack_weight(const float* __restrict__ w, int
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = transpose ? w[(size_t)(k0 + j) * c + row] : w[(size_t)row * c + k0 + j];
-  wp[(size_t)(ct * kcn + ks) * 64 + lane] = narrow8<TS>(v);
+  wp[(size_t)(ct * kcn + ks) * 64 + lane] = narrow16<TS>(v);
 }
 
 // y[b, co, p] = TS( sum_ci TS(W[co, ci]) * TS(act(c0[b,ci]*in0[b,ci,p] + c1[b,ci]*in1[b,ci,p] + c2[b,ci])) (+ epilogue) )
@@ -183,8 +157,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cuh_kernel(const TS* __
       f32x2 tv[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        f32x2 t2 = __builtin_elementwise_fma(f32x2{c0[j], c0[j]}, HalfOps<TS>::widen2(r0[j][ep]), f32x2{c2[j], c2[j]});
-        if (TWO_IN) t2 = __builtin_elementwise_fma(f32x2{c1[j], c1[j]}, HalfOps<TS>::widen2(r1[j][ep]), t2);
+        f32x2 t2 = __builtin_elementwise_fma(f32x2{c0[j], c0[j]}, Pair<TS>::widen(r0[j][ep]), f32x2{c2[j], c2[j]});
+        if (TWO_IN) t2 = __builtin_elementwise_fma(f32x2{c1[j], c1[j]}, Pair<TS>::widen(r1[j][ep]), t2);
         if (RELU) { t2.x = fmaxf(t2.x, 0.f); t2.y = fmaxf(t2.y, 0.f); }
         if (RECORD)   // v >= 0 here: v > 0 <=> its bits != 0
           bits |= (min(__float_as_uint(t2.x), 1u) << (8 * j + 2 * ep)) | (min(__float_as_uint(t2.y), 1u) << (8 * j + 2 * ep + 1));
@@ -193,7 +167,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cuh_kernel(const TS* __
 #pragma unroll
       for (int o = 0; o < 2; ++o) {
         const int e = 2 * ep + o;
-        const u32x2 pk = {HalfOps<TS>::narrow2(f32x2{tv[0][o], tv[1][o]}), HalfOps<TS>::narrow2(f32x2{tv[2][o], tv[3][o]})};
+        const u32x2 pk = {Pair<TS>::narrow(f32x2{tv[0][o], tv[1][o]}), Pair<TS>::narrow(f32x2{tv[2][o], tv[3][o]})};
         int wa;
         asm("v_xor_b32 %0, %1, %2" : "=v"(wa) : "n"(cuh_swz_c(e) << 4), "v"(wbase));
         *reinterpret_cast<u32x2*>(dst + wa + e * ROWB) = pk;
@@ -267,15 +241,15 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cuh_kernel(const TS* __
           float s1 = 0.f, s2 = 0.f;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            pk[i] = HalfOps<TS>::narrow2(f32x2{o[2 * i] + bs, o[2 * i + 1] + bs});
-            const f32x2 d = HalfOps<TS>::widen2(pk[i]) - f32x2{bs, bs};   // what is stored, shifted by the bias
+            pk[i] = Pair<TS>::narrow(f32x2{o[2 * i] + bs, o[2 * i + 1] + bs});
+            const f32x2 d = Pair<TS>::widen(pk[i]) - f32x2{bs, bs};   // what is stored, shifted by the bias
             s1 += d.x + d.y;
             s2 += d.x * d.x + d.y * d.y;
           }
           ws1[k] += oct_ok ? s1 : 0.f;
           ws2[k] += oct_ok ? s2 : 0.f;
         } else {
-          pk = narrow8<TS>(o);
+          pk = narrow16<TS>(o);
         }
         const int soff = 8 * k * row_bytes + p0 * 2;
         store_b128_guarded<0>(pk, ry, voff_st, soff);
@@ -416,8 +390,8 @@ __global__ __launch_bounds__(512, 1) void pw_wgrad_h_kernel(const TS* __restrict
       for (int j = 0; j < NJ; ++j) {
         const float k0 = op ? cfb[j][0] : cfa[j][0], k1 = op ? cfb[j][1] : cfa[j][1], k2 = op ? cfb[j][2] : cfa[j][2];
         float x0[8], x1[8], v[8];
-        widen8<TS>(raw[op][0][j], x0);
-        if (two) widen8<TS>(raw[op][1][j], x1);
+        widen16<TS>(raw[op][0][j], x0);
+        if (two) widen16<TS>(raw[op][1][j], x1);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float t = fmaf(k0, x0[e], k2);
@@ -427,7 +401,7 @@ __global__ __launch_bounds__(512, 1) void pw_wgrad_h_kernel(const TS* __restrict
         }
         const int row = 64 * j + ld_row;
         const int unit = (row >> 5) * 64 + (((row & 31) + 32 * it_h) ^ ch8);
-        ldsh[buf * kBuf + (it_ks * 2 + op) * kOp + unit] = narrow8<TS>(v);
+        ldsh[buf * kBuf + (it_ks * 2 + op) * kOp + unit] = narrow16<TS>(v);
       }
     }
   };

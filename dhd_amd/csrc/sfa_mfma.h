@@ -4,17 +4,14 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "vec16.h"
 
 namespace dhd_sfa {
 
+using namespace dhd;   // vec16.h: f32x4, f32x2, u32x4, u32x2, bf16x2, pack_bf16 / unpack_bf16, Pair, widen16 / narrow16
+
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 
 // two floats -> packed bf16 pairs (a in the low half = lower k) of the three terms.
 // Round-to-nearest-even cuts (v_cvt_pk_bf16_f32, one instruction per pair): h = bf16(x), m = bf16(x - h),
@@ -22,11 +19,6 @@ using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 // 8, so l is exact too): h + m + l == x.  Compared with cuts by truncation the parts are up to 4x smaller
 // (|x - h| <= 2^-9 |x|, |x - h - m| <= 2^-17 |x|), which matters for the three-product mode where the terms
 // am*bm, al*bh, ah*bl are dropped: worst case 3 * 2^-18 |ab| per product.
-__device__ __forceinline__ unsigned pack_bf16(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
-__device__ __forceinline__ f32x2 unpack_bf16(unsigned p) {
-  f32x2 r = {__uint_as_float(p << 16), __uint_as_float(p & 0xffff0000u)};
-  return r;
-}
 __device__ __forceinline__ void split2(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
   const f32x2 x = {a, b};
   h = pack_bf16(x);

@@ -523,32 +523,20 @@ __global__ __launch_bounds__(kEwBlock) void pair_sums_kernel(const float* __rest
 
 // Four consecutive elements of the stage's edge tensors (out, gout, gx: dhd_sfa_weights.io_dtype) as float32: 16 bytes of
 // float32, 8 bytes of a half type (widened exactly / rounded to nearest even).
-template <class T> __device__ __forceinline__ f32x4 ld4(const T* base, size_t i4);
-template <> __device__ __forceinline__ f32x4 ld4<float>(const float* base, size_t i4) {
-  return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base) + i4);
+template <class T> __device__ __forceinline__ f32x4 ld4(const T* base, size_t i4) {
+  if constexpr (std::is_same_v<T, float>) {
+    return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base) + i4);
+  } else {
+    const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(base) + i4);
+    const f32x2 a = Pair<T>::widen(w.x), b = Pair<T>::widen(w.y);
+    return f32x4{a.x, a.y, b.x, b.y};
+  }
 }
-template <> __device__ __forceinline__ f32x4 ld4<_Float16>(const _Float16* base, size_t i4) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 v = __builtin_nontemporal_load(reinterpret_cast<const h4*>(base) + i4);
-  return f32x4{(float)v.x, (float)v.y, (float)v.z, (float)v.w};
-}
-template <> __device__ __forceinline__ f32x4 ld4<__bf16>(const __bf16* base, size_t i4) {
-  const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(base) + i4);
-  return f32x4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
-}
-template <class T> __device__ __forceinline__ void st4(T* base, size_t i4, f32x4 v);
-template <> __device__ __forceinline__ void st4<float>(float* base, size_t i4, f32x4 v) {
-  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(base) + i4);
-}
-template <> __device__ __forceinline__ void st4<_Float16>(_Float16* base, size_t i4, f32x4 v) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-  __builtin_nontemporal_store(h, reinterpret_cast<h4*>(base) + i4);
-}
-template <> __device__ __forceinline__ void st4<__bf16>(__bf16* base, size_t i4, f32x4 v) {
-  typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-  const b4 h = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-  __builtin_nontemporal_store(h, reinterpret_cast<b4*>(base) + i4);
+// element-wise converts: the pairwise Pair<T>::narrow gives the same instructions in another order
+template <class T> __device__ __forceinline__ void st4(T* base, size_t i4, f32x4 v) {
+  typedef T t4 __attribute__((ext_vector_type(4)));
+  const t4 h = {(T)v.x, (T)v.y, (T)v.z, (T)v.w};
+  __builtin_nontemporal_store(h, reinterpret_cast<t4*>(base) + i4);
 }
 
 // out = g*(a*xb) + (1-g)*((1-a)*xv),  g = sigmoid(sc*y2 + sh)

@@ -98,19 +98,19 @@ __global__ __launch_bounds__(kEwBlock) void blend2_bn_bwd_h_kernel(const TS* __r
   float s1 = 0.f, s2 = 0.f, sa = 0.f;
   auto body = [&](const u32x4 wp, const u32x4 wq, const u32x4 ws, const u32x4 wo, int i) {
     float p[8], q[8], s[8], o[8], r[8];
-    widen8<TS>(wp, p);
-    widen8<TS>(wq, q);
-    widen8<TS>(ws, s);
-    widen8<TS>(wo, o);
+    widen16<TS>(wp, p);
+    widen16<TS>(wq, q);
+    widen16<TS>(ws, s);
+    widen16<TS>(wo, o);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float g = sigmoidf_(fmaf(sc, s[j], sh));
       r[j] = o[j] * (a * p[j] - na * q[j]) * g * (1.0f - g);
       sa = fmaf(o[j], g * p[j] - (1.0f - g) * q[j], sa);
     }
-    const u32x4 pk = narrow8<TS>(r);
+    const u32x4 pk = narrow16<TS>(r);
     __builtin_nontemporal_store(pk, reinterpret_cast<u32x4*>(rp) + i);
-    widen8<TS>(pk, r);
+    widen16<TS>(pk, r);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       s1 += r[j];
@@ -225,9 +225,9 @@ __global__ __launch_bounds__(kEwBlock) void stage_gx_h_kernel(const float* __res
   chunk_range8(hw, &lo, &hi);
   auto body = [&](const u32x4 ws, const u32x4 wo, const u32x4 wd, int i) {
     float s[8], o[8], d[8], rb[8], rv[8];
-    widen8<TS>(ws, s);
-    widen8<TS>(wo, o);
-    widen8<TS>(wd, d);
+    widen16<TS>(ws, s);
+    widen16<TS>(wo, o);
+    widen16<TS>(wd, d);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float g = sigmoidf_(fmaf(sc, s[j], sh));

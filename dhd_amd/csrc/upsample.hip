@@ -7,78 +7,23 @@
 //             adds the contributions of the <= (2 s + 2)^2 output pixels that read it, float32 accumulation, one writer per
 //             element: no atomics, no memset, deterministic (torch's kernels scatter with atomics, in half precision for half
 //             tensors, and its channels_last backward takes 2.3 ms where this one takes the time of reading the gradient once).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+#include "vec16.h"
 
 namespace {
 
 constexpr int kUpBlock = 256;
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Num;
-template <> struct Num<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ float get(const float* p) { return *p; }
-  static __device__ __forceinline__ void put(float* p, float v) { *p = v; }
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+// 16-byte vectors (channels_last kernels), plain access; the NCHW kernels read and write single elements
+template <typename T> struct Num : dhd::Vec16<T, false> {
+  static __device__ __forceinline__ float get(const T* p) {
+    if constexpr (std::is_same_v<T, __half>) return __half2float(*p);
+    else if constexpr (std::is_same_v<T, __hip_bfloat16>) return __uint_as_float((unsigned)*reinterpret_cast<const unsigned short*>(p) << 16);
+    else return *p;
   }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-  }
-};
-template <> struct Num<__half> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ float get(const __half* p) { return __half2float(*p); }
-  static __device__ __forceinline__ void put(__half* p, float v) { *p = __float2half_rn(v); }
-  static __device__ __forceinline__ void load(const __half* p, float (&v)[8]) {
-    const u32x4 t = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned w = t[i];
-      const __half2 h = *reinterpret_cast<const __half2*>(&w);
-      v[2 * i] = __low2float(h);
-      v[2 * i + 1] = __high2float(h);
-    }
-  }
-  static __device__ __forceinline__ void store(__half* p, const float (&v)[8]) {
-    u32x4 t;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const __half2 h = __floats2half2_rn(v[2 * i], v[2 * i + 1]);
-      t[i] = *reinterpret_cast<const unsigned*>(&h);
-    }
-    *reinterpret_cast<u32x4*>(p) = t;
-  }
-};
-__device__ __forceinline__ unsigned bf16_rne(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-template <> struct Num<__hip_bfloat16> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ float get(const __hip_bfloat16* p) {
-    return __uint_as_float((unsigned)*reinterpret_cast<const unsigned short*>(p) << 16);
-  }
-  static __device__ __forceinline__ void put(__hip_bfloat16* p, float v) { *reinterpret_cast<unsigned short*>(p) = (unsigned short)bf16_rne(v); }
-  static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&v)[8]) {
-    const u32x4 t = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(t[i] << 16);
-      v[2 * i + 1] = __uint_as_float(t[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ void store(__hip_bfloat16* p, const float (&v)[8]) {
-    u32x4 t;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) t[i] = bf16_rne(v[2 * i]) | (bf16_rne(v[2 * i + 1]) << 16);
-    *reinterpret_cast<u32x4*>(p) = t;
+  static __device__ __forceinline__ void put(T* p, float v) {
+    if constexpr (std::is_same_v<T, __half>) *p = __float2half_rn(v);
+    else if constexpr (std::is_same_v<T, __hip_bfloat16>) *reinterpret_cast<unsigned short*>(p) = (unsigned short)dhd::bf16_rne(v);
+    else *p = v;
   }
 };
 
@@ -252,11 +197,10 @@ int up_dispatch(bool bwd, const void* in, void* out, int dtype, int layout, int 
   if (!up_ok(dtype, layout, n, c, hin, win, hout, wout)) return DHD_EUNSUPPORTED;
   const Geom g = make_geom(n, c, hin, win, hout, wout);
   hipStream_t st = dhd_stream(stream);
-  switch (dtype) {
-    case 0: return up_run<float>(bwd, (const float*)in, (float*)out, layout, g, st);
-    case 1: return up_run<__half>(bwd, (const __half*)in, (__half*)out, layout, g, st);
-    default: return up_run<__hip_bfloat16>(bwd, (const __hip_bfloat16*)in, (__hip_bfloat16*)out, layout, g, st);
-  }
+  return dhd::with_dtype<dhd::HipHalf>(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return up_run<T>(bwd, (const T*)in, (T*)out, layout, g, st);
+  });
 }
 
 }  // namespace

@@ -6,71 +6,23 @@
 //   reverse  : out[b][y][x][:] = win[b][wy][wx][iy][ix][:] with (wy ws + iy, wx ws + ix) = ((y - shift) mod Hp, (x - shift) mod Wp)
 // Each is also the other's transpose (the gradient of one is the other applied to the gradient).  The element type may change on the
 // way (float32 LayerNorm output -> the autocast dtype the qkv projection would cast to anyway; half gradients -> float32).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+#include "vec16.h"
 
 namespace {
 
 constexpr int kWinBlock = 256;
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // eight consecutive elements <-> float registers, as 16-byte accesses
-template <typename T> struct Elem;
-template <> struct Elem<float> {
-  static __device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-    const f32x4 a = reinterpret_cast<const f32x4*>(p)[0], b = reinterpret_cast<const f32x4*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-  static __device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
-    reinterpret_cast<f32x4*>(p)[0] = f32x4{v[0], v[1], v[2], v[3]};
-    reinterpret_cast<f32x4*>(p)[1] = f32x4{v[4], v[5], v[6], v[7]};
-  }
-};
-template <> struct Elem<__half> {
-  static __device__ __forceinline__ void load8(const __half* p, float (&v)[8]) {
-    const u32x4 t = *reinterpret_cast<const u32x4*>(p);
+template <typename T> __device__ __forceinline__ void load8(const T* p, float (&v)[8]) {
+  using V = dhd::Vec16<T, false>;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned w = t[i];
-      const __half2 h = *reinterpret_cast<const __half2*>(&w);
-      v[2 * i] = __low2float(h);
-      v[2 * i + 1] = __high2float(h);
-    }
-  }
-  static __device__ __forceinline__ void store8(__half* p, const float (&v)[8]) {
-    u32x4 t;
+  for (int k = 0; k < 8; k += V::N) V::load(p + k, v + k);
+}
+template <typename T> __device__ __forceinline__ void store8(T* p, const float (&v)[8]) {
+  using V = dhd::Vec16<T, false>;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const __half2 h = __floats2half2_rn(v[2 * i], v[2 * i + 1]);
-      t[i] = *reinterpret_cast<const unsigned*>(&h);
-    }
-    *reinterpret_cast<u32x4*>(p) = t;
-  }
-};
-template <> struct Elem<__hip_bfloat16> {
-  static __device__ __forceinline__ void load8(const __hip_bfloat16* p, float (&v)[8]) {
-    const u32x4 t = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(t[i] << 16);
-      v[2 * i + 1] = __uint_as_float(t[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ void store8(__hip_bfloat16* p, const float (&v)[8]) {
-    auto rne = [](float f) {
-      const unsigned u = __float_as_uint(f);
-      return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    };
-    u32x4 t;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) t[i] = rne(v[2 * i]) | (rne(v[2 * i + 1]) << 16);
-    *reinterpret_cast<u32x4*>(p) = t;
-  }
-};
+  for (int k = 0; k < 8; k += V::N) V::store(p + k, v + k);
+}
 
 struct WinGeom {
   int b, h, w, c, ws, shift, hp, wp, nh, nw;
@@ -109,9 +61,9 @@ __global__ __launch_bounds__(kWinBlock) void window_rows(const TI* __restrict__ 
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = 0.f;
     } else {
-      Elem<TI>::load8(in + src * g.c + cg * 8, v);
+      load8<TI>(in + src * g.c + cg * 8, v);
     }
-    Elem<TO>::store8(out + row * g.c + cg * 8, v);
+    store8<TO>(out + row * g.c + cg * 8, v);
   }
 }
 
@@ -124,15 +76,6 @@ int window_launch(const void* in, void* out, const WinGeom& g, int reverse, hipS
   else hipLaunchKernelGGL((window_rows<TI, TO, false>), dim3((unsigned)blocks), dim3(kWinBlock), 0, st, (const TI*)in, (TO*)out, g);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
-}
-
-template <typename TI>
-int window_out(const void* in, void* out, int out_dtype, const WinGeom& g, int reverse, hipStream_t st) {
-  switch (out_dtype) {
-    case 0: return window_launch<TI, float>(in, out, g, reverse, st);
-    case 1: return window_launch<TI, __half>(in, out, g, reverse, st);
-    default: return window_launch<TI, __hip_bfloat16>(in, out, g, reverse, st);
-  }
 }
 
 }  // namespace
@@ -150,9 +93,9 @@ extern "C" int dhd_window_rows(const void* in, void* out, int in_dtype, int out_
   g.wp = g.nw * window;
   if ((long)b * g.hp * g.wp >= (1L << 40)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
-  switch (in_dtype) {
-    case 0: return window_out<float>(in, out, out_dtype, g, reverse, st);
-    case 1: return window_out<__half>(in, out, out_dtype, g, reverse, st);
-    default: return window_out<__hip_bfloat16>(in, out, out_dtype, g, reverse, st);
-  }
+  return dhd::with_dtype<dhd::HipHalf>(in_dtype, [&](auto* ti) {
+    return dhd::with_dtype<dhd::HipHalf>(out_dtype, [&](auto* to) {
+      return window_launch<std::remove_pointer_t<decltype(ti)>, std::remove_pointer_t<decltype(to)>>(in, out, g, reverse, st);
+    });
+  });
 }

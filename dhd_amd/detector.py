@@ -235,7 +235,7 @@ class _UpsampleBilinear(torch.autograd.Function):
         from . import _lib
         nhwc = x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
         n, c, h, w = x.shape
-        return (_lib_dtype(x.dtype), int(nhwc), n, c, h, w, int(size[0]), int(size[1]))
+        return (_lib.DTYPE_CODE.get(x.dtype, -1), int(nhwc), n, c, h, w, int(size[0]), int(size[1]))
 
     @staticmethod
     def forward(ctx, x, size):
@@ -262,10 +262,6 @@ class _UpsampleBilinear(torch.autograd.Function):
                              memory_format=torch.channels_last if geom[1] else torch.contiguous_format)
             _lib.check(lib.dhd_upsample_bilinear_backward(_lib.ptr(gy), *geom, _lib.ptr(gx), _lib.stream_ptr(gy.device)), 'dhd_upsample_bilinear_backward')
         return gx, None
-
-
-def _lib_dtype(dt):
-    return {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}.get(dt, -1)
 
 
 class Upsample(nn.Upsample):

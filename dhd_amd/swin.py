@@ -15,6 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.utils import checkpoint
 
+from . import _lib
 from .registry import BACKBONES
 
 
@@ -142,7 +143,6 @@ def shift_window_mask(H_pad, W_pad, window, shift, device):
     return torch.where(diff != 0, torch.full_like(diff, -100.0), torch.zeros_like(diff))
 
 
-_WIN_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 _PLAIN_WINDOWS = bool(__import__('os').environ.get('DHD_PLAIN_WINDOWS'))   # A/B switch: F.pad + torch.roll + permute copies
 
 
@@ -153,14 +153,13 @@ class _WindowRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, H, W, ws, sh, reverse, out_dtype):
-        from . import _lib
         x = x.contiguous()
         B, C = x.shape[0], x.shape[-1]
         nh, nw = -(-H // ws), -(-W // ws)
         shape = (B, H, W, C) if reverse else (B, nh * nw, ws * ws, C)
         with torch.cuda.device(x.device):
             out = torch.empty(shape, dtype=out_dtype, device=x.device)
-            _lib.check(_lib.load().dhd_window_rows(_lib.ptr(x), _lib.ptr(out), _WIN_DTYPES[x.dtype], _WIN_DTYPES[out_dtype], B, H, W, C, ws, sh,
+            _lib.check(_lib.load().dhd_window_rows(_lib.ptr(x), _lib.ptr(out), _lib.dtype_code(x.dtype), _lib.dtype_code(out_dtype), B, H, W, C, ws, sh,
                                                    int(reverse), _lib.stream_ptr(x.device)), 'dhd_window_rows')
         ctx.args = (H, W, ws, sh, reverse, x.dtype)
         return out
@@ -172,7 +171,7 @@ class _WindowRows(torch.autograd.Function):
 
 
 def _windows_on_gpu(x):
-    return (not _PLAIN_WINDOWS) and x.is_cuda and x.dtype in _WIN_DTYPES and x.shape[-1] % 8 == 0 and x.data_ptr() % 16 == 0
+    return (not _PLAIN_WINDOWS) and x.is_cuda and x.dtype in _lib.DTYPE_CODE and x.shape[-1] % 8 == 0 and x.data_ptr() % 16 == 0
 
 
 class ShiftWindowMSA(nn.Module):

@@ -180,6 +180,45 @@ def test_argument_validation_happens_on_the_host():
     assert lib.dhd_ema_update(None, None, None, 0, 0.5, 0.5, None) == 0  # empty state
     d.batch = 1 << 20
     assert lib.dhd_mghs_workspace_bytes(C.byref(d), C.byref(n), C.byref(m)) == -3  # beyond the int32 index space
+    # a dtype code outside DHD_F32 / DHD_F16 / DHD_BF16 is refused by every entry point that takes one, before any launch (all other
+    # arguments valid, pointers never dereferenced).  The return codes are those of the library before the dtype dispatch moved
+    # into csrc/vec16.h.  Left out because the earlier library reaches a launch with them: dhd_mghs_forward_views (gathers before it
+    # looks at the views; dhd_mghs_forward_stream_views is the same check without the gather) and dhd_mghs_softmax_backward with
+    # g_xd == NULL (xd_dtype is not read then).
+    P = C.c_void_p(0x10000)
+    d1 = _lib.MghsDesc()
+    d1.batch, d1.n_cams, d1.n_depth, d1.fh, d1.fw, d1.channels, d1.n_grids = 1, 1, 4, 4, 11, 64, 1
+    d1.grid[0].n[0], d1.grid[0].n[1], d1.grid[0].n[2] = 8, 8, 1
+    assert lib.dhd_mghs_workspace_bytes(C.byref(d1), C.byref(n), C.byref(m)) == 0
+    ws = _lib.MghsWorkspace(0x10000, n.value, 0x4000000, m.value)
+    views = (_lib.TensorView * _lib.DHD_MAX_GRIDS)()
+    views[0].ptr, views[0].batch_stride, views[0].z_stride, views[0].channel_stride = 0x8000000, 64 * 64, 64 * 64, 64
+    for bad in (3, -1):
+        assert lib.dhd_bn_train_forward(P, bad, 2, 8, 64, None, None, None, None, 0.1, 1e-5, P, P, P, P, None) == -3
+        assert lib.dhd_bn_train_backward(P, P, bad, 2, 8, 64, None, P, P, P, None, None, P, None) == -3
+        assert lib.dhd_bn_nhwc_train_forward(P, None, bad, 128, 8, 0, None, None, None, None, 0.1, 1e-5, P, P, P, P, P, None) == -3
+        assert lib.dhd_bn_nhwc_train_backward(P, None, P, bad, 128, 8, 0, None, P, P, None, P, None, None, None, P, None) == -3
+        assert lib.dhd_upsample_bilinear_forward(P, bad, 0, 1, 8, 4, 4, 8, 8, P, None) == -3
+        assert lib.dhd_upsample_bilinear_backward(P, bad, 1, 1, 8, 4, 4, 8, 8, P, None) == -3
+        assert lib.dhd_window_rows(P, P, bad, 0, 1, 7, 7, 8, 7, 0, 0, None) == -3                       # input code
+        assert lib.dhd_window_rows(P, P, 0, bad, 1, 7, 7, 8, 7, 0, 1, None) == -3                       # output code
+        assert lib.dhd_deform_im2col_t(P, 0, P, P, bad, 1, 4, 5, 5, 3, 1, 1, None) == -1                # column code
+        assert lib.dhd_deform_im2col_t(P, bad, P, P, 0, 1, 4, 5, 5, 3, 1, 1, None) == -1                # image code
+        assert lib.dhd_deform_col2im_t(P, bad, P, 0, P, P, P, 1, 4, 5, 5, 3, 1, 1, P, 1 << 20, None) == -3
+        assert lib.dhd_deform_col2im_t(P, 0, P, bad, P, P, P, 1, 4, 5, 5, 3, 1, 1, P, 1 << 20, None) == -1
+        assert lib.dhd_mghs_softmax_forward(P, bad, 0, 12, None, 0, 0, 0, 2, 44, 4, 8, 0, None, None, P, P, None, None, None) == -1
+        assert lib.dhd_mghs_softmax_forward(P, 0, 0, 12, P, bad, 0, 8, 2, 44, 4, 8, 8, None, None, P, P, P, None, None) == -1
+        assert lib.dhd_mghs_softmax_backward(None, None, None, None, None, 2, 44, 4, 8, 0, P, bad, 0, 12, None, 0, 0, 0, None) == -1
+        assert lib.dhd_mghs_softmax_backward(None, None, None, None, None, 2, 44, 4, 8, 8, P, 0, 0, 12, P, bad, 0, 8, None) == -1
+        views[0].dtype = bad
+        assert lib.dhd_mghs_forward_stream_views(C.byref(d1), P, P, C.byref(views), C.byref(ws), None) == -1
+        assert lib.dhd_mghs_backward_views(C.byref(d1), P, P, C.byref(views), P, P, C.byref(ws), None) == -1
+    # a mixed pair the deform kernels are not built for (half image, other half columns), and a half view on the generic MGHS path
+    assert lib.dhd_deform_im2col_t(P, 1, P, P, 2, 1, 4, 5, 5, 3, 1, 1, None) == -1
+    d1.channels, views[0].dtype = 32, 1
+    assert lib.dhd_mghs_workspace_bytes(C.byref(d1), C.byref(n), C.byref(m)) == 0
+    ws = _lib.MghsWorkspace(0x10000, n.value, 0x4000000, m.value)
+    assert lib.dhd_mghs_backward_views(C.byref(d1), P, P, C.byref(views), P, P, C.byref(ws), None) == -3
 
 
 def test_no_silent_fallback_without_gpu_or_library():
