@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DHD_AMD_LIB', os.path.join(_HERE, 'csrc', 'libdhd_amd.so'))
 
 DHD_MAX_GRIDS = 4
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _ERRORS = {-1: 'DHD_EINVAL (bad argument)', -2: 'DHD_ENOSPACE (workspace too small)',
            -3: 'DHD_EUNSUPPORTED (size outside supported range)'}
@@ -73,6 +73,7 @@ class SfaWeights(C.Structure):
 
 
 SFA_GEMM = {'default': 0, 'bf16x6': 1, 'f32': 2, 'bf16x3': 3}   # dhd_sfa_weights.gemm
+SFA_INFER = {'auto': 0, 'unfused': 1, 'two_pass': 2, 'one_pass': 3}   # dhd_sfa_stage_infer: form
 
 
 class SfaGrads(C.Structure):
@@ -128,6 +129,9 @@ _PROTOTYPES = {
     'dhd_sfa_stage_backward': ([_P, C.POINTER(SfaWeights), _P, _P, _P, C.POINTER(SfaGrads), _P, _I, _I, _I, _P], _I),
     'dhd_sfa_stage_forward_phase': ([_P, C.POINTER(SfaWeights), _P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
     'dhd_sfa_stage_backward_phase': ([_P, C.POINTER(SfaWeights), _P, _P, _P, C.POINTER(SfaGrads), _P, _I, _I, _I, _I, _P, _P], _I),
+    'dhd_sfa_stage_infer_supported': ([_I] * 5, _I),
+    'dhd_sfa_stage_infer_scratch_bytes': ([_I] * 7 + [C.POINTER(C.c_size_t)], _I),
+    'dhd_sfa_stage_infer': ([_P, C.POINTER(SfaWeights), _P, _P, _I, _I, _I, _I, _P], _I),
     'dhd_occ_loss_workspace_bytes': ([], C.c_size_t),
     'dhd_occ_loss_forward': ([_P, _P, _P, _P, C.c_int64, _I, _I, _I, _P, _P, _P], _I),
     'dhd_occ_loss_backward': ([_P, _P, _P, _P, C.c_int64, _I, _I, _I, _P, _P, _P, _P], _I),

@@ -40,11 +40,26 @@ __host__ __device__ inline int cu_swz(int p) { return ((((p >> 2) & 7) ^ (p & 1)
 
 // dynamic LDS of a workgroup: the double-buffered activation tile + one store patch per wave + the prologue coefficient
 // tables [nb][3][c] of the launch's samples + the bias [c]
-inline size_t cu_lds_bytes(int c, int waves, int nb) {
-  return (size_t)2 * 2 * 32 * 2 * c + (size_t)waves * 32 * kCuPatchPitch * sizeof(float) + ((size_t)nb * 3 + 1) * c * sizeof(float);
+// (blend, EPI 3: + the epilogue's tables, a [nb][c] and the BatchNorm-2 scale | shift [2][c])
+inline size_t cu_lds_bytes(int c, int waves, int nb, bool blend = false) {
+  return (size_t)2 * 2 * 32 * 2 * c + (size_t)waves * 32 * kCuPatchPitch * sizeof(float) + ((size_t)nb * 3 + 1) * c * sizeof(float) +
+         (blend ? ((size_t)nb + 2) * c * sizeof(float) : 0);
 }
 // samples per launch: as many as have their coefficient tables next to the tiles and patches in 160 KB of LDS
-inline int cu_max_batch(int c, int waves) { return (int)((160 * 1024 - cu_lds_bytes(c, waves, 0)) / ((size_t)3 * c * sizeof(float))); }
+inline int cu_max_batch(int c, int waves, bool blend = false) {
+  return (int)((160 * 1024 - cu_lds_bytes(c, waves, 0, blend)) / ((size_t)(blend ? 4 : 3) * c * sizeof(float)));
+}
+
+// EPI 3 (forward-only inference, conv2): the forward epilogue continued through BatchNorm-2, the sigmoid and the final blend
+// out = g*(a*x_bev) + (1-g)*((1-a)*x_voxel), g = sigmoid(sc*y2 + sh) -- the expression of blend2_bn_kernel / blend2_bn_h_kernel
+// (sfa_stage.hip, sfa_stage_half.h) on the 4 (8) pixels of one channel a lane holds after the patch transpose.  y2 is never stored.
+struct CuBlend {
+  const void* x;        // (nb, 2C, HW) in the storage type: x_bev | x_voxel of the launch's samples
+  const float* a1;      // [nb][C] channel attention
+  const float* scsh;    // [2][C] BatchNorm-2 scale | shift
+  void* out;            // (nb, C, HW) in the I/O type
+};
+__device__ __forceinline__ float cu_sigmoid(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
 // ReLU pass bits of the cu kernels: one 16-bit word per (tile, 32-row group, staging lane); bit 4*j + e = row 4*g + j of
 // the group, pixel 4*q + e of the tile (lane = 8*g + q): one bit per activation, C 32-bit words per tile.
@@ -74,18 +89,18 @@ __device__ __forceinline__ void cu_pack_weight(const float* __restrict__ w, int 
 }
 
 // EPI: 0 forward (+ bias, BatchNorm partial sums of the un-biased result), 1 data gradient with the recorded ReLU pass bits,
-// 2 plain.  RECORD (with RELU): the prologue leaves the pass bits of its ReLU for the backward's EPI 1.
+// 2 plain, 3 forward + BatchNorm-2 + sigmoid + final blend, storing `out` (CuBlend; element type TO) instead of y.  RECORD (with RELU): the prologue leaves the pass bits of its ReLU for the backward's EPI 1.
 // ABL (experiments/gemm_cu_bench.hip only; 0 in the product): 1 no MFMAs, 2 no result stores, 4 no epilogue at all,
 // 8 no activation loads (stale registers are staged), 16 no staging, 32 no B-fragment LDS reads (MFMAs on registers),
 // 64 shader clocks of the workgroup (s_memtime) into stat_part, 128 s_sleep in place of the MFMAs (with 1), 256 shader clocks per
 // phase and wave into stat_part
 template <int KCN, int WAVES, bool TWO_IN, bool RELU, int EPI, bool RECORD, int AUX, int R, int NACC, int ABL = 0, int SAUX = 0, bool PP = false,
-          int BPF = 0, int EORD = 0>
+          int BPF = 0, int EORD = 0, class TO = float>
 __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* __restrict__ in0, const float* __restrict__ in1,
                                                                    size_t in_bstride, unsigned in_bytes, const float* __restrict__ coef,
                                                                    const u32x4* __restrict__ wp, const float* __restrict__ bias,
                                                                    unsigned* __restrict__ relu_mask, float* __restrict__ stat_part,
-                                                                   float* __restrict__ y, int hw, int nb, int contig) {
+                                                                   float* __restrict__ y, int hw, int nb, int contig, CuBlend bl) {
   constexpr int C = 16 * KCN;
   constexpr int MT = C / (32 * WAVES);          // 32-channel output tiles (= 32-row input groups) per wave
   static_assert(MT >= 1 && MT * 32 * WAVES == C, "C = 32 * MT * WAVES");
@@ -223,8 +238,15 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
     for (int k = 0; k < 4; ++k) ws1[mt][k] = ws2[mt][k] = 0.f;
   // the bias goes to LDS behind the coefficient tables (read per tile in the epilogue: 4 registers less)
   float* bias_lds = cf_lds + nb * 3 * C;
-  if (EPI == 0)
+  if (EPI == 0 || EPI == 3)
     for (int i = tid; i < C; i += WAVES * 64) bias_lds[i] = bias[i];
+  // EPI 3: a [nb][C] | BatchNorm-2 scale [C] | shift [C] behind the bias
+  float* bl_a = bias_lds + C;
+  float* bl_sc = bl_a + nb * C;
+  if (EPI == 3) {
+    for (int i = tid; i < nb * C; i += WAVES * 64) bl_a[i] = bl.a1[i];
+    for (int i = tid; i < 2 * C; i += WAVES * 64) bl_sc[i] = bl.scsh[i];
+  }
 
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   // Everything requested so far (weights, bias, coefficient table) is complete before the tile loop, unconditionally: otherwise
@@ -258,6 +280,22 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
 #pragma unroll
         for (int k = 0; k < 4; ++k)
           mask_r[mt][k] = reinterpret_cast<const unsigned short*>(relu_mask)[((size_t)t * (C / 32) + wv * MT + mt) * 64 + 8 * ((g >> 2) + 2 * k) + q];
+    }
+    // EPI 3: the x_bev / x_voxel quads of this lane's output channels, requested here so that they arrive behind the MFMA
+    // phase and the staging (they are consumed within the iteration: the loop header's pending-load state does not change)
+    f32x4 xb[MT][4], xv[MT][4];
+    if (EPI == 3) {
+      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(static_cast<const float*>(bl.x)) + (size_t)b * 2 * C * hw, 0, (unsigned)((size_t)2 * C * hw * sizeof(float)), 0x00020000);
+      const int voff = (p0 + 4 * q < hw) ? st_voff : st_voff - 16 * q;   // beyond the row's end: quad 0 again, never stored
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int soff = (32 * mt + 8 * k) * row_bytes + p0 * 4;
+          xb[mt][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, soff, AUX));
+          xv[mt][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, soff + C * row_bytes, AUX));
+        }
     }
     // ---- MFMA phase: D[channel][pixel] over all K ---------------------------------------------------------------------
     const unsigned char* src = cu_lds + PAR * BUFB;
@@ -358,6 +396,29 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
           for (int e = 0; e < 4; ++e) o[e] = __int_as_float(__float_as_int(o[e]) & __builtin_amdgcn_sbfe(w4, e, 1));
         }
         const int soff = (32 * mt + 8 * k) * row_bytes + p0 * 4;
+        if (EPI == 3) {
+          const int ch = kbase + 32 * mt + g + 8 * k;
+          const float bs = bias_lds[ch];
+          o.x += bs; o.y += bs; o.z += bs; o.w += bs;                // y2, as the forward stores it
+          const float a = bl_a[b * C + ch], na = 1.0f - a, sc = bl_sc[ch], sh = bl_sc[C + ch];
+          const f32x4 pb = xb[mt][k], pv = xv[mt][k];
+          f32x4 r;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float gt = cu_sigmoid(fmaf(sc, o[j], sh));
+            r[j] = gt * (a * pb[j]) + (1.0f - gt) * (na * pv[j]);
+          }
+          const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
+              static_cast<TO*>(bl.out) + (size_t)b * C * hw, 0, (unsigned)((size_t)C * hw * sizeof(TO)), 0x00020000);
+          if constexpr (std::is_same_v<TO, float>) {
+            store_b128_guarded<SAUX>(__builtin_bit_cast(u32x4, r), ro, voff_st, soff);
+          } else {                                                   // 4 pixels of a half type: 8 bytes (no store-data hazard)
+            typedef TO t4 __attribute__((ext_vector_type(4)));
+            const t4 hv = {(TO)r.x, (TO)r.y, (TO)r.z, (TO)r.w};
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hv), ro, quad_ok ? st_voff >> 1 : 0x7ffffff0, soff >> 1, SAUX);
+          }
+          continue;
+        }
         if (!(ABL & 2)) store_b128_guarded<SAUX>(__builtin_bit_cast(u32x4, o), ry, voff_st, soff);
       }
     }

@@ -22,6 +22,9 @@
 //   * BatchNorm gradient sums are per-plane streaming reductions with double-precision finalisation; the blends are fused with
 //     the BatchNorm affine and the sigmoid.
 // Forward reads x three times and y1/y2 twice; nothing is transposed, there is no NHWC detour.
+// Forward-only inference (dhd_sfa_stage_infer, running statistics, nothing kept for a backward): stage_infer below -- the forward's
+// own launches, conv2 with BatchNorm-2 + sigmoid + blend in its epilogue (x three times, y1 twice), or under half storage both
+// convolutions per pixel tile (sfa_half.h: sfa_onepass_h_kernel; x twice).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -343,12 +346,10 @@ __global__ __launch_bounds__(kEwBlock) void bn_train_finalize_kernel(const float
   }
 }
 
-__global__ __launch_bounds__(kEwBlock) void bn_eval_coef_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                const float* __restrict__ run_mean, const float* __restrict__ run_var,
-                                                                float eps, float* __restrict__ mean, float* __restrict__ rstd,
-                                                                float* __restrict__ scsh, float* __restrict__ tab, int nb, int c) {
-  const int ch = blockIdx.x * kEwBlock + threadIdx.x;
-  if (ch >= c) return;
+__device__ __forceinline__ void bn_eval_coef_channel(int ch, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     const float* __restrict__ run_mean, const float* __restrict__ run_var, float eps,
+                                                     float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ scsh,
+                                                     float* __restrict__ tab, int nb, int c) {
   const float rs = 1.0f / sqrtf(run_var[ch] + eps);
   mean[ch] = run_mean[ch];
   rstd[ch] = rs;
@@ -361,6 +362,28 @@ __global__ __launch_bounds__(kEwBlock) void bn_eval_coef_kernel(const float* __r
     t[c + ch] = 0.f;
     t[2 * c + ch] = shf;
   }
+}
+
+__global__ __launch_bounds__(kEwBlock) void bn_eval_coef_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                const float* __restrict__ run_mean, const float* __restrict__ run_var,
+                                                                float eps, float* __restrict__ mean, float* __restrict__ rstd,
+                                                                float* __restrict__ scsh, float* __restrict__ tab, int nb, int c) {
+  const int ch = blockIdx.x * kEwBlock + threadIdx.x;
+  if (ch >= c) return;
+  bn_eval_coef_channel(ch, gamma, beta, run_mean, run_var, eps, mean, rstd, scsh, tab, nb, c);
+}
+
+// both layers' tables in one launch (forward-only inference: nothing lies between them); blockIdx.y = layer
+struct BnEvalJob {
+  const float *gamma, *beta, *run_mean, *run_var;
+  float eps;
+  float *mean, *rstd, *scsh, *tab;
+};
+__global__ __launch_bounds__(kEwBlock) void bn_eval_coef2_kernel(BnEvalJob j1, BnEvalJob j2, int nb, int c) {
+  const int ch = blockIdx.x * kEwBlock + threadIdx.x;
+  if (ch >= c) return;
+  const BnEvalJob& j = blockIdx.y ? j2 : j1;
+  bn_eval_coef_channel(ch, j.gamma, j.beta, j.run_mean, j.run_var, j.eps, j.mean, j.rstd, j.scsh, j.tab, nb, c);
 }
 
 // BatchNorm backward coefficients: dy = c0*g + c1*y + c2 (per channel), dgamma, dbeta, and the
@@ -676,7 +699,7 @@ __global__ __launch_bounds__(kEwBlock) void plane_mean_pack_kernel(const float* 
   if ((int)blockIdx.y < n_planes) { plane_mean_block(x, part, hw, sm); return; }
   const int pb = ((int)blockIdx.y - n_planes) * kPlaneChunks + (int)blockIdx.x;
   const int which = pb / job.blocks_each;
-  if (which >= 4) return;
+  if (which >= 4 || job.dst[which] == nullptr) return;   // (forward-only inference packs no transposes)
   if (job.cu) cu_pack_weight(job.w[which & 1], which >> 1, job.dst[which], job.c, (pb % job.blocks_each) * kEwBlock + (int)threadIdx.x);
   else pack_weight_res_block(job.w[which & 1], which >> 1, job.dst[which], job.c, job.cob, job.nt, pb % job.blocks_each);
 }
@@ -1168,12 +1191,15 @@ int make_plan(const dhd_sfa_weights* w, int c, int hw, Plan* p) {
 // x_bev / x_voxel, bias epilogue), conv2 (BatchNorm + ReLU prologue, records the ReLU pass bits), the data gradients through
 // conv2 (BatchNorm-backward prologue over g2 / y2, ReLU mask epilogue) and through conv1.  A weight gradient's second operand is
 // the input of conv1 or conv2 and takes that GEMM's prologue.
-enum Op { kConv1, kConv2, kDgrad2, kDgrad1 };
+// kConv2Blend (forward-only inference, cu / cuh kernels): conv2 whose epilogue goes on through BatchNorm-2, the sigmoid and the
+// final blend and stores `out`; no y2, no pass bits, no statistics.
+enum Op { kConv1, kConv2, kDgrad2, kDgrad1, kConv2Blend };
 template <int OP>
 struct Variant {
-  static constexpr bool two = OP != kConv2;     // two inputs
-  static constexpr bool relu = OP == kConv2;    // ReLU after the prologue
-  static constexpr int epi = OP == kDgrad2 ? 1 : OP == kDgrad1 ? 2 : 0;   // 0 forward (+bias), 1 dgrad with ReLU mask, 2 dgrad plain
+  static constexpr bool two = OP != kConv2 && OP != kConv2Blend;     // two inputs
+  static constexpr bool relu = OP == kConv2 || OP == kConv2Blend;    // ReLU after the prologue
+  // 0 forward (+bias), 1 dgrad with ReLU mask, 2 dgrad plain, 3 forward + blend epilogue
+  static constexpr int epi = OP == kDgrad2 ? 1 : OP == kDgrad1 ? 2 : OP == kConv2Blend ? 3 : 0;
   static constexpr bool rec = OP == kConv2;     // records the ReLU pass bits
 };
 template <class F>
@@ -1183,6 +1209,7 @@ int with_op(Op op, F&& f) {
     case kConv2: return f(Variant<kConv2>{});
     case kDgrad2: return f(Variant<kDgrad2>{});
     case kDgrad1: return f(Variant<kDgrad1>{});
+    case kConv2Blend: return f(Variant<kConv2Blend>{});
   }
   return DHD_EUNSUPPORTED;
 }
@@ -1203,6 +1230,8 @@ struct GemmCall {
   TS* y;
   const TS* aux;             // f32 dgrad 2: y1 and BatchNorm-1, the ReLU mask recomputed
   const float* aux_scsh;
+  CuBlend blend;             // kConv2Blend: x, a, BatchNorm-2 scale / shift, out (y is unused)
+  int out_dtype;             // kConv2Blend on float32 storage: element type of blend.out
 };
 
 // One-CU-per-pixel-tile kernels: pw_gemm_cu (float32 storage, sfa_gemm_cu.h) and pw_gemm_cuh (half storage, sfa_half.h)
@@ -1210,7 +1239,8 @@ template <class TS>
 int launch_gemm_cu(const GemmCall<TS>& g, int b, int c, int hw, hipStream_t st, int* stat_rows) {
   constexpr bool kHalf = !std::is_same<TS, float>::value;
   const int waves = c / 32;
-  const int max_b = kHalf ? cuh_max_batch(c, waves) : cu_max_batch(c, waves);
+  const bool blend = g.op == kConv2Blend;
+  const int max_b = kHalf ? cuh_max_batch(c, waves, blend) : cu_max_batch(c, waves, blend);
   if (max_b < 1) return DHD_EUNSUPPORTED;
   const unsigned in_bytes = (unsigned)((size_t)g.in_channels * hw * sizeof(TS));
   const int nwt = kHalf ? (hw + kCuhTile - 1) / kCuhTile : (hw + 31) / 32;
@@ -1221,7 +1251,7 @@ int launch_gemm_cu(const GemmCall<TS>& g, int b, int c, int hw, hipStream_t st, 
     const int nb = b - b0 < max_b ? b - b0 : max_b;
     const long total = (long)nb * nwt;
     const int grid = (int)(total < cus ? total : cus);
-    const size_t shmem = kHalf ? cuh_lds_bytes(c, waves, nb) : cu_lds_bytes(c, waves, nb);
+    const size_t shmem = kHalf ? cuh_lds_bytes(c, waves, nb, blend) : cu_lds_bytes(c, waves, nb, blend);
     const TS* i0 = g.in0 + (size_t)b0 * g.in_bstride;
     const TS* i1 = g.in1 ? g.in1 + (size_t)b0 * g.in_bstride : nullptr;
     const float* cf = g.coef + (size_t)b0 * 3 * c;
@@ -1230,6 +1260,15 @@ int launch_gemm_cu(const GemmCall<TS>& g, int b, int c, int hw, hipStream_t st, 
     float* sp = g.stat_part ? g.stat_part + (size_t)rows_done * 2 * c : nullptr;
     rows_done += grid;                                   // one statistics row per workgroup
     TS* yo = g.y + (size_t)b0 * c * hw;
+    CuBlend bl = g.blend;
+    if (blend) {
+      const size_t osz = kHalf ? sizeof(TS) : g.out_dtype == DHD_F32 ? 4 : 2;
+      bl.x = static_cast<const TS*>(bl.x) + (size_t)b0 * 2 * c * hw;
+      bl.a1 += (size_t)b0 * c;
+      bl.out = static_cast<char*>(bl.out) + (size_t)b0 * c * hw * osz;
+      if (kHalf) yo = static_cast<TS*>(bl.out);   // half storage: out is of the storage type and takes y's place
+      else yo = static_cast<TS*>(g.blend.out);    // (unused; any valid address for the pipeline fill's dropped stores)
+    }
     // EORD: with two inputs the epilogue goes before the staging (which waits for twice the loads), with one input after it --
     // measured either way (experiments/gemm_cu_bench.hip): 100 vs 107 us (conv1), 96 vs 97 (dgrad), 82 vs 76 (conv2).
     // float32: <KCN, WAVES, TWO_IN, RELU, EPI, RECORD, AUX = nt loads, R = 1, NACC = 1, ABL = 0, SAUX = 0, PP = ping-pong, BPF = 0,
@@ -1238,12 +1277,21 @@ int launch_gemm_cu(const GemmCall<TS>& g, int b, int c, int hw, hipStream_t st, 
       using V = decltype(v);
       auto run = [&](auto kcn) {
         constexpr int KCN = decltype(kcn)::value, WAVES = KCN / 2, EORD = V::two ? 1 : 0;
-        if constexpr (kHalf)
+        if constexpr (kHalf) {
           return launch_lds<pw_gemm_cuh_kernel<TS, KCN, WAVES, V::two, V::relu, V::epi, V::rec, EORD>>(
-              dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb);
-        else
-          return launch_lds<pw_gemm_cu_kernel<KCN, WAVES, V::two, V::relu, V::epi, V::rec, 2, 1, 1, 0, 0, true, 0, EORD>>(
-              dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb, 1);
+              dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb, bl);
+        } else {
+          auto go = [&](auto* to) {
+            using TO = std::remove_pointer_t<decltype(to)>;
+            return launch_lds<pw_gemm_cu_kernel<KCN, WAVES, V::two, V::relu, V::epi, V::rec, 2, 1, 1, 0, 0, true, 0, EORD, TO>>(
+                dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb, 1, bl);
+          };
+          if constexpr (V::epi == 3) {
+            if (g.out_dtype == DHD_F16) return go((_Float16*)nullptr);
+            if (g.out_dtype == DHD_BF16) return go((__bf16*)nullptr);
+          }
+          return go((float*)nullptr);
+        }
       };
       return c == 256 ? run(IntC<16>{}) : run(IntC<8>{});
     });
@@ -1284,9 +1332,13 @@ int launch_gemm_res(const Plan& p, const GemmCall<float>& g, int b, int c, int h
     const int rc = with_op(g.op, [&](auto v) {
       using V = decltype(v);
       auto run = [&](auto nt, auto cob, auto kcn) {
-        return launch_lds<pw_gemm_res_kernel<decltype(nt)::value, decltype(cob)::value, decltype(kcn)::value, V::two, V::relu, V::epi,
-                                             kResWaves, 0, 4>>(grid, dim3(kResWaves * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride,
-                                                               in_bytes, cf, wp, g.bias, rm, sp, yo, c, hw, nb, groups, nteams);
+        if constexpr (V::epi == 3) {   // the blend epilogue exists in the cu / cuh kernels only
+          return (int)DHD_EUNSUPPORTED;
+        } else {
+          return launch_lds<pw_gemm_res_kernel<decltype(nt)::value, decltype(cob)::value, decltype(kcn)::value, V::two, V::relu, V::epi,
+                                               kResWaves, 0, 4>>(grid, dim3(kResWaves * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride,
+                                                                 in_bytes, cf, wp, g.bias, rm, sp, yo, c, hw, nb, groups, nteams);
+        }
       };
       // (terms, tiles per workgroup) by channel count, as make_plan selects them
       if (p.nt == 3 && p.cob == 4 && c == 128) return run(IntC<3>{}, IntC<4>{}, IntC<8>{});
@@ -1331,6 +1383,8 @@ int launch_gemm_streamed(const Plan& p, const GemmCall<float>& g, int b, int c, 
     using V = decltype(v);
     auto run = [&](auto cot_c) {
       constexpr int COT = decltype(cot_c)::value;
+      if constexpr (V::epi == 3) return (int)DHD_EUNSUPPORTED;   // the blend epilogue exists in the cu / cuh kernels only
+      else {
       if (!six)
         return launch_lds<pw_gemm_kernel<COT, V::two, V::relu, V::epi>>(grid, dim3(kPwBlock), shmem, shmem, st, g.in0, g.in1, g.in_bstride,
                                                                         g.coef, static_cast<const float*>(g.wp), g.bias, g.aux, g.aux_scsh,
@@ -1346,6 +1400,7 @@ int launch_gemm_streamed(const Plan& p, const GemmCall<float>& g, int b, int c, 
                                                                        g.in1, g.in_bstride, in_bytes, g.coef, wp, g.bias, g.mask,
                                                                        g.stat_part, g.y, c, hw, t_main, tps, 1);
       return (int)DHD_OK;
+      }
     };
     return cot == 8 ? run(IntC<8>{}) : run(IntC<4>{});
   });
@@ -1643,6 +1698,120 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
   return DHD_OK;
 }
 
+// Forward-only inference (dhd_sfa_stage_infer): running statistics, nothing kept for a backward.
+//   UNFUSED   stage_forward itself, its `saved` layout placed at the head of `scratch`: every Plan
+//   TWO_PASS  Gemm::cu / Gemm::cuh: mean + weight pack, fc, both BatchNorm tables, conv1 -> y1, conv2 + blend epilogue -> out
+//   ONE_PASS  Gemm::cuh: mean + weight pack, fc, both BatchNorm tables, sfa_onepass_h_kernel (sfa_half.h) -> out; no y1
+// Every form returns the bytes of stage_forward(training = 0): same kernels up to y1, and the blend epilogue applies
+// blend2_bn(_h)_kernel's expression to the value the unfused conv2 would have stored.
+inline bool infer_form_exists(const Plan& p, int form) {
+  switch (form) {
+    case DHD_SFA_INFER_AUTO: case DHD_SFA_INFER_UNFUSED: return true;
+    case DHD_SFA_INFER_TWO_PASS: return p.gemm == Gemm::cu || p.gemm == Gemm::cuh;
+    case DHD_SFA_INFER_ONE_PASS: return p.gemm == Gemm::cuh;
+    default: return false;
+  }
+}
+inline int infer_resolve(const Plan& p, int form) {
+  if (form != DHD_SFA_INFER_AUTO) return form;
+  // measured at (4, 2C, 200, 200), alternating windows (profiles/r7/sfa_infer*.json): one-pass beats two-pass by 6 us of 161 at
+  // C = 256 and by 30 us of 105 at C = 128 in both half types (two-pass against itself: <= 0.3 us)
+  if (infer_form_exists(p, DHD_SFA_INFER_ONE_PASS)) return DHD_SFA_INFER_ONE_PASS;
+  return infer_form_exists(p, DHD_SFA_INFER_TWO_PASS) ? DHD_SFA_INFER_TWO_PASS : DHD_SFA_INFER_UNFUSED;
+}
+
+// scratch of the two-pass form: the two weight images, the small float32 tables, y1
+struct InferLayout {
+  size_t wp1, wp2, mean_part, s, h, a1, tab_a, mean1, rstd1, scsh1, tab1, mean2, rstd2, scsh2, tab2, y1, total;
+};
+inline InferLayout infer_layout(int b, int c, int hw, int r, int storage, bool with_y1) {
+  const bool half = storage != DHD_F32;
+  const size_t cc = (size_t)c * c;
+  InferLayout L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  auto f = [&](size_t n) { return take(n * sizeof(float)); };
+  L.wp1 = take(half ? 2 * cc : 8 * cc); L.wp2 = take(half ? 2 * cc : 8 * cc);
+  L.mean_part = f((size_t)b * 2 * c * kPlaneChunks);
+  L.s = f((size_t)b * 2 * c); L.h = f((size_t)b * r); L.a1 = f((size_t)b * c); L.tab_a = f((size_t)b * 3 * c);
+  L.mean1 = f(c); L.rstd1 = f(c); L.scsh1 = f(2 * c); L.tab1 = f((size_t)b * 3 * c);
+  L.mean2 = f(c); L.rstd2 = f(c); L.scsh2 = f(2 * c); L.tab2 = f((size_t)b * 3 * c);   // tab2: bn2 feeds no GEMM prologue (a sink)
+  L.y1 = take(with_y1 ? (size_t)b * c * hw * (half ? 2 : 4) : 0);
+  L.total = o;
+  return L;
+}
+
+inline size_t infer_scratch_total(const Plan& p, int form, int b, int c, int hw, int r) {
+  const int f = infer_resolve(p, form);
+  if (f != DHD_SFA_INFER_UNFUSED) return infer_layout(b, c, hw, r, p.storage, f == DHD_SFA_INFER_TWO_PASS).total;
+  return saved_layout(b, c, hw, r, p.storage).total + scratch_layout(b, c, hw, r, p.storage).total;
+}
+
+// sfa_onepass_h_kernel: one workgroup per CU, contiguous tile ranges; as many samples per launch as have their tables in LDS
+template <class TS>
+int launch_onepass(const TS* x, const OnePassArgs& A, TS* out, int b, int c, int hw, hipStream_t st) {
+  const int max_b = onepass_max_batch(c);
+  if (max_b < 1) return DHD_EUNSUPPORTED;
+  const int nwt = (hw + kCuhTile - 1) / kCuhTile;
+  int cus = cu_count();
+  if (cus <= 0) cus = 256;
+  for (int b0 = 0; b0 < b; b0 += max_b) {
+    const int nb = b - b0 < max_b ? b - b0 : max_b;
+    const long total = (long)nb * nwt;
+    const int grid = (int)(total < cus ? total : cus);
+    OnePassArgs a = A;
+    a.tab_a += (size_t)b0 * 3 * c;
+    a.a1 += (size_t)b0 * c;
+    const TS* xi = x + (size_t)b0 * 2 * c * hw;
+    TS* oi = out + (size_t)b0 * c * hw;
+    const size_t shmem = onepass_lds_bytes(c, nb);
+    const int rc = c == 256 ? launch_lds<sfa_onepass_h_kernel<TS, 16>>(dim3(grid), dim3(kOnePassWaves * 64), shmem, kLdsBytes, st, xi, a, oi, hw, nb)
+                            : launch_lds<sfa_onepass_h_kernel<TS, 8>>(dim3(grid), dim3(kOnePassWaves * 64), shmem, kLdsBytes, st, xi, a, oi, hw, nb);
+    if (rc != DHD_OK) return rc;
+  }
+  return DHD_OK;
+}
+
+template <class TS, class TO>
+int stage_infer(const Plan& p, const TS* x, const dhd_sfa_weights* w, TO* out, void* scratch, int b, int c, int hw, int form,
+                hipStream_t st) {
+  const int r = w->hidden;
+  char* sc = static_cast<char*>(scratch);
+  form = infer_resolve(p, form);
+  if (form == DHD_SFA_INFER_UNFUSED)
+    return stage_forward<TS, TO>(p, x, w, out, sc, sc + saved_layout(b, c, hw, r, p.storage).total, b, c, hw, 0, 2, nullptr, st);
+  const InferLayout L = infer_layout(b, c, hw, r, p.storage, form == DHD_SFA_INFER_TWO_PASS);
+  auto F = [&](size_t off) { return reinterpret_cast<float*>(sc + off); };
+  TS* y1 = reinterpret_cast<TS*>(sc + L.y1);
+  const size_t cs = (size_t)c * hw;
+  void* const dst[4] = {sc + L.wp1, sc + L.wp2, nullptr, nullptr};
+  int rc = launch_mean_pack(p, x, w->conv1_w, w->conv2_w, dst, F(L.mean_part), b, c, hw, st);
+  if (rc != DHD_OK) return rc;
+  hipLaunchKernelGGL(fc_forward_kernel, dim3(b), dim3(kFcBlock), (size_t)(2 * c + r) * sizeof(float), st, F(L.mean_part), w->fc1_w, w->fc1_b,
+                     w->fc2_w, w->fc2_b, F(L.s), F(L.h), F(L.a1), F(L.tab_a), c, r, hw, static_cast<int*>(nullptr), 0);
+  DHD_LAUNCH_CHECK();
+  const BnEvalJob j1 = {w->bn1_w, w->bn1_b, w->bn1_mean, w->bn1_var, w->eps1, F(L.mean1), F(L.rstd1), F(L.scsh1), F(L.tab1)};
+  const BnEvalJob j2 = {w->bn2_w, w->bn2_b, w->bn2_mean, w->bn2_var, w->eps2, F(L.mean2), F(L.rstd2), F(L.scsh2), F(L.tab2)};
+  hipLaunchKernelGGL(bn_eval_coef2_kernel, dim3(dhd_cdiv(c, kEwBlock), 2), dim3(kEwBlock), 0, st, j1, j2, b, c);
+  DHD_LAUNCH_CHECK();
+  if (form == DHD_SFA_INFER_ONE_PASS) {
+    if constexpr (std::is_same<TS, float>::value) {
+      return DHD_EUNSUPPORTED;
+    } else {
+      const OnePassArgs A = {F(L.tab_a), F(L.tab1), w->conv1_b, w->conv2_b, F(L.a1), F(L.scsh2), reinterpret_cast<const u32x4*>(sc + L.wp1),
+                             reinterpret_cast<const u32x4*>(sc + L.wp2)};
+      return launch_onepass<TS>(x, A, reinterpret_cast<TS*>(out), b, c, hw, st);
+    }
+  }
+  // y1 = conv1(blend1(x))
+  rc = launch_gemm(p, GemmCall<TS>{kConv1, x, x + cs, 2 * cs, c, F(L.tab_a), sc + L.wp1, w->conv1_b, nullptr, nullptr, y1}, b, c, hw, st);
+  if (rc != DHD_OK) return rc;
+  // out = blend2(x, a, sigmoid(bn2(conv2(relu(bn1(y1))))))
+  return launch_gemm(p, GemmCall<TS>{kConv2Blend, y1, nullptr, cs, c, F(L.tab1), sc + L.wp2, w->conv2_b, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, CuBlend{x, F(L.a1), F(L.scsh2), out}, w->io_dtype},
+                     b, c, hw, st);
+}
+
 // The driver instance of a call: storage type, and on float32 storage the I/O type
 template <class F>
 int with_types(const Plan& p, int io_dtype, F&& f) {
@@ -1687,6 +1856,34 @@ static int stage_backward_entry(const void* x, const dhd_sfa_weights* w, const v
     return stage_backward<TS, TO>(p, static_cast<const TS*>(x), w, saved, static_cast<const TO*>(gout), static_cast<TO*>(gx), grads,
                                   scratch, b, c, hw, lo, hi, sync, dhd_stream(stream));
   });
+}
+
+static int stage_infer_entry(const void* x, const dhd_sfa_weights* w, void* out, void* scratch, int b, int c, int hw, int form,
+                             void* stream) {
+  if (!x || !w || !out || !scratch || b <= 0 || form < DHD_SFA_INFER_AUTO || form > DHD_SFA_INFER_ONE_PASS) return DHD_EINVAL;
+  if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
+  if (!w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b || !w->conv1_w || !w->conv1_b || !w->bn1_w || !w->bn1_b || !w->conv2_w ||
+      !w->conv2_b || !w->bn2_w || !w->bn2_b)
+    return DHD_EINVAL;
+  if (w->training) return DHD_EINVAL;   // batch statistics belong to dhd_sfa_stage_forward
+  if (!w->bn1_mean || !w->bn1_var || !w->bn2_mean || !w->bn2_var) return DHD_EINVAL;
+  Plan p;
+  if (int rc = make_plan(w, c, hw, &p); rc != DHD_OK) return rc;
+  if (!infer_form_exists(p, form)) return DHD_EUNSUPPORTED;
+  return with_types(p, w->io_dtype, [&](auto* ts, auto* to) {
+    using TS = std::remove_pointer_t<decltype(ts)>;
+    using TO = std::remove_pointer_t<decltype(to)>;
+    return stage_infer<TS, TO>(p, static_cast<const TS*>(x), w, static_cast<TO*>(out), scratch, b, c, hw, form, dhd_stream(stream));
+  });
+}
+
+// the Plan of a (storage type, precision) without a weights struct of the caller's
+static int infer_plan(int c, int hw, int storage_dtype, int gemm, Plan* p) {
+  dhd_sfa_weights w = {};
+  w.gemm = gemm;
+  w.storage_dtype = w.io_dtype = storage_dtype;
+  if (!stage_supported(c, hw)) return DHD_EUNSUPPORTED;
+  return make_plan(&w, c, hw, p);
 }
 
 }  // namespace
@@ -1742,6 +1939,25 @@ int dhd_sfa_stage_backward_phase(const void* x, const dhd_sfa_weights* w, const 
                                  void* stream) {
   if (phase < 0 || phase > 2 || !sync_sums || (reinterpret_cast<uintptr_t>(sync_sums) & 7)) return DHD_EINVAL;
   return stage_backward_entry(x, w, saved, gout, gx, grads, scratch, b, c, hw, phase, phase, sync_sums, stream);
+}
+
+int dhd_sfa_stage_infer_supported(int c, int hw, int storage_dtype, int gemm, int form) {
+  Plan p;
+  return infer_plan(c, hw, storage_dtype, gemm, &p) == DHD_OK && infer_form_exists(p, form) ? 1 : 0;
+}
+
+int dhd_sfa_stage_infer_scratch_bytes(int b, int c, int hw, int hidden, int storage_dtype, int gemm, int form, size_t* bytes) {
+  if (b <= 0 || hidden <= 0 || !bytes || form < DHD_SFA_INFER_AUTO || form > DHD_SFA_INFER_ONE_PASS) return DHD_EINVAL;
+  Plan p;
+  if (int rc = infer_plan(c, hw, storage_dtype, gemm, &p); rc != DHD_OK) return rc;
+  if (!infer_form_exists(p, form)) return DHD_EUNSUPPORTED;
+  *bytes = infer_scratch_total(p, form, b, c, hw, hidden);
+  return DHD_OK;
+}
+
+int dhd_sfa_stage_infer(const void* x, const dhd_sfa_weights* w, void* out, void* scratch, int b, int c, int hw, int form,
+                        void* stream) {
+  return stage_infer_entry(x, w, out, scratch, b, c, hw, form, stream);
 }
 
 }  // extern "C"

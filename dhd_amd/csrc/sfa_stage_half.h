@@ -24,7 +24,7 @@ __global__ __launch_bounds__(kEwBlock) void plane_mean_pack_h_kernel(const TS* _
   if ((int)blockIdx.y >= n_planes) {
     const int pb = ((int)blockIdx.y - n_planes) * kPlaneChunks + (int)blockIdx.x;
     const int which = pb / job.blocks_each;
-    if (which < 4)
+    if (which < 4 && job.dst[which] != nullptr)   // (forward-only inference packs no transposes)
       cuh_pack_weight<TS>(job.w[which & 1], which >> 1, job.dst[which], job.c, (pb % job.blocks_each) * kEwBlock + (int)threadIdx.x);
     return;
   }

@@ -138,6 +138,46 @@ def _stage_params(stage):
             sp[0].weight, sp[0].bias, sp[1].weight, sp[1].bias, sp[3].weight, sp[3].bias, sp[4].weight, sp[4].bias)
 
 
+def _stage_input(stage, x, c, hw):
+    """(x as the operator reads it, I/O dtype, half storage?) -- the dtype rules of the fused stage, see _FusedStage.forward."""
+    io_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else torch.float32
+    half_storage = (io_dtype != torch.float32 and stage.half_storage
+                    and bool(_lib.load().dhd_sfa_stage_half_storage_supported(c, hw)))
+    if half_storage:
+        x = _lib.require_gpu_tensor(x.contiguous(), io_dtype, 'SFA input')
+    else:
+        x = _lib.require_gpu_tensor(x.float().contiguous(), torch.float32, 'SFA input')
+    if x.data_ptr() % 16:
+        x = x.clone()
+    return x, io_dtype, half_storage
+
+
+def _stage_weights(stage, params, io_dtype, half_storage):
+    """dhd_sfa_weights of this call, and the parameter tensors it points to (keep them alive as long as the struct)."""
+    bn1, bn2 = stage.spacial_leanring[1], stage.spacial_leanring[4]
+    ps = [_lib.require_gpu_tensor(p.detach().contiguous(), torch.float32, 'SFA ' + n) for n, p in zip(_STAGE_PARAMS, params)]
+    wts = _lib.SfaWeights()
+    for n, p in zip(_STAGE_PARAMS, ps):
+        setattr(wts, n, p.data_ptr())
+    # batch statistics iff nn.BatchNorm2d would use them (train mode, or no running buffers)
+    training = int(bn1.training or bn1.running_mean is None)
+    if training != int(bn2.training or bn2.running_mean is None):
+        raise _lib.DhdError('SFA: the two BatchNorm layers of the stage must be in the same mode')
+    for tag, bn in (('bn1', bn1), ('bn2', bn2)):
+        track = bn.running_mean is not None
+        setattr(wts, tag + '_mean', bn.running_mean.data_ptr() if track else None)
+        setattr(wts, tag + '_var', bn.running_var.data_ptr() if track else None)
+    wts.hidden, wts.training = ps[0].shape[0], training
+    wts.gemm = _lib.SFA_GEMM[stage.gemm or default_gemm()]   # per call; backward reuses this struct
+    wts.io_dtype = _lib.dtype_code(io_dtype)
+    wts.storage_dtype = wts.io_dtype if half_storage else 0
+    wts.eps1, wts.eps2 = bn1.eps, bn2.eps
+    (wts.momentum1, wts.bn1_batches), (wts.momentum2, wts.bn2_batches) = _bn_momentum(bn1, training), _bn_momentum(bn2, training)
+    if training and not bn1.training:
+        wts.bn1_mean = wts.bn1_var = wts.bn2_mean = wts.bn2_var = None
+    return wts, ps
+
+
 class _FusedStage(torch.autograd.Function):
     """The whole stage in libdhd_amd.so (dhd_sfa_stage_forward/backward): the 1x1 convolutions on
     the f32 MFMA with the blends, BatchNorm and ReLU fused into their operand paths."""
@@ -149,45 +189,17 @@ class _FusedStage(torch.autograd.Function):
         # arithmetic, saved tensors and parameters are float32; the stage's result then leaves in x's dtype (dhd_sfa_weights.
         # io_dtype: rounded to nearest even, what the next convolution's cast would make of a float32 result), the gradient comes
         # back in that dtype and the input gradient is returned in it -- no float32 round trips of (B,C,H,W) / (B,2C,H,W) tensors
-        io_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else torch.float32
         b, c2, h, w = x.shape
         c, hw = c2 // 2, h * w
         # HALF STORAGE (dhd_sfa_weights.storage_dtype, ABI 4): a half x is read as it is and every (B,C,H,W) tensor the operator
         # keeps or passes between its kernels stays in that type -- the reference's own formulation under autocast (mix.py:37-59
         # with DHD-S.py:281); float32 arithmetic, statistics, parameters and parameter gradients.  C == 128 / 256, hw % 8 == 0;
         # otherwise (or with stage.half_storage = False) x is widened once and only the edges are half (ABI 3 behaviour)
-        half_storage = (io_dtype != torch.float32 and stage.half_storage
-                        and bool(_lib.load().dhd_sfa_stage_half_storage_supported(c, hw)))
-        if half_storage:
-            x = _lib.require_gpu_tensor(x.contiguous(), io_dtype, 'SFA input')
-        else:
-            x = _lib.require_gpu_tensor(x.float().contiguous(), torch.float32, 'SFA input')
-        if x.data_ptr() % 16:
-            x = x.clone()
+        x, io_dtype, half_storage = _stage_input(stage, x, c, hw)
         dev = x.device
         lib = _lib.load()
-        bn1, bn2 = stage.spacial_leanring[1], stage.spacial_leanring[4]
-        ps = [_lib.require_gpu_tensor(p.detach().contiguous(), torch.float32, 'SFA ' + n) for n, p in zip(_STAGE_PARAMS, params)]
-        hidden = ps[0].shape[0]
-        wts = _lib.SfaWeights()
-        for n, p in zip(_STAGE_PARAMS, ps):
-            setattr(wts, n, p.data_ptr())
-        # batch statistics iff nn.BatchNorm2d would use them (train mode, or no running buffers)
-        training = int(bn1.training or bn1.running_mean is None)
-        if training != int(bn2.training or bn2.running_mean is None):
-            raise _lib.DhdError('SFA: the two BatchNorm layers of the stage must be in the same mode')
-        for tag, bn in (('bn1', bn1), ('bn2', bn2)):
-            track = bn.running_mean is not None
-            setattr(wts, tag + '_mean', bn.running_mean.data_ptr() if track else None)
-            setattr(wts, tag + '_var', bn.running_var.data_ptr() if track else None)
-        wts.hidden, wts.training = hidden, training
-        wts.gemm = _lib.SFA_GEMM[stage.gemm or default_gemm()]   # per call; backward reuses this struct
-        wts.io_dtype = _lib.dtype_code(io_dtype)
-        wts.storage_dtype = wts.io_dtype if half_storage else 0
-        wts.eps1, wts.eps2 = bn1.eps, bn2.eps
-        (wts.momentum1, wts.bn1_batches), (wts.momentum2, wts.bn2_batches) = _bn_momentum(bn1, training), _bn_momentum(bn2, training)
-        if training and not bn1.training:
-            wts.bn1_mean = wts.bn1_var = wts.bn2_mean = wts.bn2_var = None
+        wts, ps = _stage_weights(stage, params, io_dtype, half_storage)
+        hidden = wts.hidden
         group = _sync_group(stage)   # None, or the process group whose ranks share BatchNorm statistics (nn.SyncBatchNorm)
         with torch.cuda.device(dev):
             nsaved, nscratch = C.c_size_t(), C.c_size_t()
@@ -247,6 +259,43 @@ class _FusedStage(torch.autograd.Function):
                         _all_reduce_sum(sums, ctx.group)
         need = ctx.needs_input_grad
         return (gx if need[0] else None, None) + tuple(g if n else None for g, n in zip(gps, need[2:]))
+
+
+def inference_selected(stage, x):
+    """True when a call of the (fused) stage takes the forward-only inference operator: `stage.infer`, both BatchNorms
+    normalise with running statistics, and nothing needs a gradient -- grad mode is off, or neither x nor any stage parameter
+    requires one.  Asks nothing of a device."""
+    if not stage.infer:
+        return False
+    sp = stage.spacial_leanring
+    for bn in (sp[1], sp[4]):
+        if bn.training or bn.running_mean is None or bn.running_var is None:
+            return False
+    if not torch.is_grad_enabled():
+        return True
+    return not (x.requires_grad or any(p is not None and p.requires_grad for p in _stage_params(stage)))
+
+
+@traced('dhd.sfa.stage.infer')
+def _infer_stage(x, stage):
+    """The stage through dhd_sfa_stage_infer: no `saved` tensor, scratch from the pool, no autograd node."""
+    b, c2, h, w = x.shape
+    c, hw = c2 // 2, h * w
+    x, io_dtype, half_storage = _stage_input(stage, x.detach(), c, hw)
+    dev = x.device
+    lib = _lib.load()
+    wts, ps = _stage_weights(stage, _stage_params(stage), io_dtype, half_storage)
+    form = _lib.SFA_INFER[stage.infer_form or 'auto']
+    with torch.cuda.device(dev):
+        nscratch = C.c_size_t()
+        _lib.check(lib.dhd_sfa_stage_infer_scratch_bytes(b, c, hw, wts.hidden, wts.storage_dtype, wts.gemm, form, C.byref(nscratch)),
+                   'dhd_sfa_stage_infer_scratch_bytes')
+        scratch = _stage_scratch(dev, nscratch.value)
+        out = torch.empty((b, c, h, w), dtype=io_dtype, device=dev)
+        _lib.check(lib.dhd_sfa_stage_infer(_lib.ptr(x), C.byref(wts), _lib.ptr(out), _lib.ptr(scratch), b, c, hw, form,
+                                           _lib.stream_ptr(dev)), 'dhd_sfa_stage_infer')
+    del ps
+    return out
 
 
 def needs_cross_rank_statistics(stage):
@@ -316,9 +365,15 @@ class channel_spatial_stage(nn.Module):
     # in the environment makes round 4's form (half edges, float32 inside) the default, for A/B runs
     half_storage = __import__('os').environ.get('DHD_SFA_HALF_STORAGE', '1') != '0'
     gemm = None   # 'bf16x3' | 'bf16x6' | 'f32': precision of the fused stage's C x C GEMMs; None = default_gemm()
+    # eval mode with nothing to differentiate (inference_selected): the forward-only operator dhd_sfa_stage_infer, which keeps
+    # no state for a backward; False: _FusedStage as in training, for A/B runs
+    infer = True
+    infer_form = None   # 'auto' | 'unfused' | 'two_pass' | 'one_pass': form of the inference operator; None = 'auto'
 
     def forward(self, x):
         if self.fused and fused_stage_supported(self, x):
+            if inference_selected(self, x):
+                return _infer_stage(x, self)
             return _FusedStage.apply(x, self, *_stage_params(self))
         params = list(self.fc.parameters()) + list(self.spacial_leanring.parameters())
         out = _AttentionStage.apply(x.float(), self, *params)

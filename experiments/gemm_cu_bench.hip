@@ -124,7 +124,7 @@ int main(int argc, char** argv) {
     CK(hipMemset(y, 0xff, (size_t)B* plane * 4));                                                                          \
     auto launch = [&] {                                                                                                    \
       hipLaunchKernelGGL(kern, dim3(cus), dim3(WAVES * 64), lds, 0, x, TWO ? x + plane : nullptr, 2 * plane,               \
-                         (unsigned)(plane * 4), coef, wp, bias, mask, stat, y, HW, B, contig);                             \
+                         (unsigned)(plane * 4), coef, wp, bias, mask, stat, y, HW, B, contig, CuBlend{});                             \
     };                                                                                                                     \
     const double us = time_kernel(launch);                                                                                 \
     const double bytes = (double)B * plane * 4 * ((TWO ? 2 : 1) + 1);                                                      \
@@ -174,7 +174,7 @@ int main(int argc, char** argv) {
       static bool once = false;                                                                                            \
       if (!once) { CK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; } \
       hipLaunchKernelGGL(kern, dim3(cus), dim3(WAVES * 64), lds, 0, x, TWO ? x + plane : nullptr, 2 * plane,               \
-                         (unsigned)(plane * 4), coef, wp, bias, mask, stat, y, HW, B, contig);                             \
+                         (unsigned)(plane * 4), coef, wp, bias, mask, stat, y, HW, B, contig, CuBlend{});                             \
     }
     auto c1_0 = NEWQ(8, true, false, 0, false, 2, 1, 1, true, 0, 1, 1);
     auto c1_1 = NEWQ(8, true, false, 0, false, 2, 1, 1, true, 1, 1, 1);

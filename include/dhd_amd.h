@@ -34,7 +34,7 @@ extern "C" {
 #define DHD_ENOSPACE (-2)   /* workspace too small */
 #define DHD_EUNSUPPORTED (-3)
 
-#define DHD_ABI_VERSION 5
+#define DHD_ABI_VERSION 6
 int dhd_abi_version(void);
 
 /* ------------------------------------------------------------------------------------ *
@@ -348,6 +348,8 @@ int dhd_sfa_mean_backward(const float* gs, float* gx, int b, int c2, int hw, voi
  *    dhd_sfa_weights.gemm; single half products under dhd_sfa_weights.storage_dtype) with the
  *    blends / BatchNorm / ReLU fused into their operand paths (csrc/sfa_stage.hip, sfa_gemm_cu.h,
  *    sfa_half.h); only the conv outputs y1, y2 and one ReLU pass bit per activation are kept for backward.
+ *    dhd_sfa_stage_infer (ABI 6) is the forward-only form for running statistics: it keeps nothing for a backward, and where
+ *    the weight images fit a CU's registers it never stores y2 or the pass bits (half storage: nor y1) at all.
  *    Supported: C == 128 or C % 256 == 0, hw % 4 == 0, 2*C*hw*4 bytes < 4 GiB (dhd_sfa_stage_supported); other shapes
  *    return DHD_EUNSUPPORTED and callers use the section-3 kernels around library convolutions.
  * ------------------------------------------------------------------------------------ */
@@ -447,6 +449,30 @@ int dhd_sfa_stage_forward_phase(const void* x, const dhd_sfa_weights* w, void* o
 int dhd_sfa_stage_backward_phase(const void* x, const dhd_sfa_weights* w, const void* saved, const void* gout,
                                  void* gx, const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw,
                                  int phase, double* sync_sums /*[dev] 2C+1*/, void* stream);
+
+/* Forward-only inference operator (ABI 6): the stage with running statistics (w->training must be 0) and no state for a
+ * backward.  The result is bit-identical to dhd_sfa_stage_forward with training = 0 for the same x, weights, gemm, io_dtype
+ * and storage_dtype, in every form; running statistics, bn*_batches and the parameters are only read.  `form` is a per-call
+ * argument (nothing process-wide):
+ *   DHD_SFA_INFER_UNFUSED   the launch sequence of dhd_sfa_stage_forward with its `saved` layout placed inside `scratch`:
+ *                           exists wherever the forward does (every channel count, precision and storage type)
+ *   DHD_SFA_INFER_TWO_PASS  conv1 -> y1 (scratch); conv2 carries bias, BatchNorm-2, the sigmoid and the final blend in its
+ *                           epilogue and stores `out`: no y2, no pass bits, one launch and two tensor passes less.  bf16x3 with
+ *                           float32 storage and half storage, C == 128 or 256
+ *   DHD_SFA_INFER_ONE_PASS  both convolutions per pixel tile, y1 handed from the first MFMA phase to the second through LDS: one
+ *                           read of x besides the mean pass, one write of out.  Half storage, C == 128 or 256 (float32 storage:
+ *                           two two-part weight images do not fit a CU's registers at C == 256)
+ *   DHD_SFA_INFER_AUTO      ONE_PASS where it exists, else TWO_PASS, else UNFUSED
+ * A form that does not exist for a shape / precision returns DHD_EUNSUPPORTED (dhd_sfa_stage_infer_supported: 1 / 0).
+ * `scratch` (dhd_sfa_stage_infer_scratch_bytes, a multiple of 16) is reusable between calls on one stream. */
+#define DHD_SFA_INFER_AUTO     0  /* the library's choice for this shape / precision */
+#define DHD_SFA_INFER_UNFUSED  1  /* the kernels of dhd_sfa_stage_forward; y1, y2, tables live in scratch */
+#define DHD_SFA_INFER_TWO_PASS 2  /* conv1 -> y1 (scratch); conv2 with the sigmoid + blend epilogue -> out */
+#define DHD_SFA_INFER_ONE_PASS 3  /* both convolutions per pixel tile; y1 never leaves the CU */
+int dhd_sfa_stage_infer_supported(int c, int hw, int storage_dtype, int gemm, int form);
+int dhd_sfa_stage_infer_scratch_bytes(int b, int c, int hw, int hidden, int storage_dtype, int gemm, int form, size_t* bytes);
+int dhd_sfa_stage_infer(const void* x, const dhd_sfa_weights* w, void* out /* w->io_dtype */, void* scratch,
+                        int b, int c, int hw, int form, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
  * 5. Occupancy-head losses (models/dense_heads/occ_head.py:102-139, predictor.loss): the
