@@ -74,6 +74,8 @@ class SfaWeights(C.Structure):
 
 SFA_GEMM = {'default': 0, 'bf16x6': 1, 'f32': 2, 'bf16x3': 3}   # dhd_sfa_weights.gemm
 SFA_INFER = {'auto': 0, 'unfused': 1, 'two_pass': 2, 'one_pass': 3}   # dhd_sfa_stage_infer: form
+RAY_PHASE = {'test': 0, 'train': 1}   # dhd_ray_render_forward: phase
+RAY_ORIGIN_F64 = 1                    # dhd_ray_iou_accumulate: flags
 
 
 class SfaGrads(C.Structure):
@@ -166,6 +168,10 @@ _PROTOTYPES = {
     'dhd_bn_nhwc_workspace_bytes': ([C.c_long, _I], C.c_size_t),
     'dhd_bn_nhwc_train_forward': ([_P, _P, _I, C.c_long, _I, _I, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P], _I),
     'dhd_bn_nhwc_train_backward': ([_P, _P, _P, _I, C.c_long, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    'dhd_ray_render_forward': ([_P] * 4 + [_I] * 8 + [_P] * 4, _I),
+    'dhd_ray_iou_supported': ([_I] * 5, _I),
+    'dhd_ray_iou_accumulate': ([_P, _P] + [_I] * 4 + [_P, _P, _I, _I, _P, _I, C.POINTER(C.c_float), C.c_float, _I, _I,
+                                                    C.POINTER(C.c_float), _I, _P, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

@@ -696,6 +696,43 @@ int dhd_transpose_batched(const void* in, void* out, int elem_bytes, long batch,
 int dhd_window_rows(const void* in, void* out, int in_dtype, int out_dtype, int b, int h, int w, int c, int window,
                     int shift, int reverse, void* stream);
 
+/* ------------------------------------------------------------------------------------ *
+ * 13. Ray-cast evaluation: RayIoU (core/evaluation/ray_metrics.py) and the voxel ray caster it rests on
+ *     (lib/dvr/dvr.cu:70-319, render_forward_cuda_kernel, "test" phase).  A ray is walked voxel by voxel in double
+ *     precision (Amanatides-Woo; ties go to y over x and to z over both; at most 1001 steps, whatever the input); its
+ *     result is the first occupied voxel on the way, else the last voxel inside the grid, and the ray parameter at which
+ *     that voxel is left.  A ray that never enters the grid keeps the initial values: distance -1, voxel (0, 0, 0).
+ *     Limits (dhd_ray_iou_supported): nx * ny * nz < 2^31, n_classes <= 32, 1..4 thresholds; beyond them DHD_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------ */
+#define DHD_RAY_PHASE_TEST 0
+#define DHD_RAY_PHASE_TRAIN 1   /* only clamps gt_dist in the reference and has no caller: DHD_EUNSUPPORTED */
+#define DHD_RAY_ORIGIN_F64 1    /* dhd_ray_iou_accumulate.flags: origins are double[n_pairs][3] (else float) */
+
+/* The reference's dvr.render_forward: sigma [dev] float (n, t_sigma, nz, ny, nx), occupied where > 0.5 (t_sigma = 1: one
+ * static grid for every t); origin (n, t_origin, 3) and points (n, m, 3) in voxel units; tindex (n, m) float, the origin
+ * of each ray, < 0 = padded ray.  Outputs, every element written: pred_dist (n, m) and gt_dist (n, m) (origin to end
+ * point), both -1 for a padded or never-entered ray; coord_index (n, m, 3) = (x, y, z) as floats, 0 likewise. */
+int dhd_ray_render_forward(const float* sigma, const float* origin, const float* points, const float* tindex, int n, int t_sigma,
+                           int t_origin, int m, int nz, int ny, int nx, int phase, float* pred_dist, float* gt_dist,
+                           float* coord_index, void* stream);
+
+int dhd_ray_iou_supported(int nx, int ny, int nz, int n_classes, int n_thresholds);
+
+/* RayIoU's counters for n_pairs (sample, lidar origin) pairs in one launch.  pred, gt: [dev] uint8 class ids
+ * (n_samples, nx, ny, nz), the layout of dhd_occ_argmax_hist's pred; a voxel is occupied where id < free_id.
+ * sample_id [dev] int32[n_pairs] (a pair whose id is outside [0, n_samples) is skipped); origins [dev] float or double
+ * [n_pairs][3] in metres; rays [dev] float[n_rays][3] unit directions.  lower (float[3], grid corner), thresholds
+ * (float[n_thresholds], metres) are HOST arrays read during the call.  Each (pair, ray) is cast through both grids:
+ * end point = ray + origin, both to voxel units by (p - lower) / voxel_size in the origins' precision rounded to float32
+ * (ray_metrics.py:101-105), distance * voxel_size and the label at the result voxel (:117-127); rays whose gt label is
+ * free_id are dropped (:191).  counts [dev] int64[(2 + n_thresholds) * n_classes] = gt_cnt | pred_cnt | tp_cnt[j]
+ * (calc_metrics, :138-166), ACCUMULATED into (zero it once per evaluation); integer sums, so the result does not depend
+ * on the order of pairs, calls or ranks.  Nothing per ray is written to memory. */
+int dhd_ray_iou_accumulate(const uint8_t* pred, const uint8_t* gt, int n_samples, int nx, int ny, int nz, const int32_t* sample_id,
+                           const void* origins, int n_pairs, int flags, const float* rays, int n_rays, const float* lower,
+                           float voxel_size, int free_id, int n_classes, const float* thresholds, int n_thresholds,
+                           int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
