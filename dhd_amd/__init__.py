@@ -16,6 +16,7 @@ from .ema import ModelEMA, MEGVIIEMAHook, SyncbnControlHook, SequentialControlHo
 from .config import Config  # noqa: F401
 from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noqa: F401
 from .amp_weights import HalfWeightCache  # noqa: F401
+from .occ_head import occ_head_infer  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'

@@ -78,6 +78,11 @@ RAY_PHASE = {'test': 0, 'train': 1}   # dhd_ray_render_forward: phase
 RAY_ORIGIN_F64 = 1                    # dhd_ray_iou_accumulate: flags
 
 
+class OccHeadWeights(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ('w1', 'b1', 'w2', 'b2')] +
+                [(n, C.c_int32) for n in ('c', 'hidden', 'dz', 'n_classes', 'gemm')])
+
+
 class SfaGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ('fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'conv1_w', 'conv1_b', 'bn1_w', 'bn1_b',
@@ -172,6 +177,9 @@ _PROTOTYPES = {
     'dhd_ray_iou_supported': ([_I] * 5, _I),
     'dhd_ray_iou_accumulate': ([_P, _P] + [_I] * 4 + [_P, _P, _I, _I, _P, _I, C.POINTER(C.c_float), C.c_float, _I, _I,
                                                     C.POINTER(C.c_float), _I, _P, _P], _I),
+    'dhd_occ_head_infer_supported': ([_I] * 7, _I),
+    'dhd_occ_head_infer_scratch_bytes': ([C.POINTER(OccHeadWeights), _I, C.POINTER(C.c_size_t)], _I),
+    'dhd_occ_head_infer': ([_P, _I, _I, C.POINTER(OccHeadWeights), _I, _I, _I] + [_P] * 7, _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

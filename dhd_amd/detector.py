@@ -527,6 +527,61 @@ class predictor(nn.Module):
             loss_voxel_sem_scal=self.weight_sem * sem_scal_loss_with_mask(preds, sem, mask),
             loss_voxel_geo_scal=self.weight_geo * geo_scal_loss_with_mask(preds, sem, mask, non_empty_idx=17))
 
+    # Opt-in: in eval mode with nothing to differentiate DHD.simple_test_occ takes predict_occ's fused operator instead of
+    # forward + get_occ.  Off by default: at near-ties of the two largest logits its class can differ from rocBLAS float32's.
+    fused_infer = False
+
+    def fused_applies(self, img_feats):
+        """True when predict_occ runs the HIP operator (dhd_amd/occ_head.py) on `img_feats`; otherwise it falls back to
+        get_occ(forward(img_feats))."""
+        if not (self.use_predicter and torch.is_tensor(img_feats) and img_feats.is_cuda):
+            return False
+        if torch.is_grad_enabled() and (img_feats.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        from . import occ_head
+        lin1, lin2 = self.predicter[0], self.predicter[2]
+        # final_conv keeps the spatial size and hands over out_dim channels in the dtype the convolution runs in
+        dt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else img_feats.dtype
+        probe = torch.empty(0, self.out_dim, 1, 1, dtype=dt, device=img_feats.device)
+        return img_feats.dim() == 4 and occ_head.supported(probe, lin1.weight, lin2.weight, self.Dz)
+
+    def predict_occ(self, img_feats, labels=None, mask_camera=None, hist=None, to_host=True, return_logits=False):
+        """The class map of get_occ(forward(img_feats)) without the logits in between: final_conv in torch, then the fused
+        operator (Linear -> Softplus -> Linear -> argmax, csrc/occ_head.hip).  to_host=True: a list of (Dx, Dy, Dz) uint8 numpy
+        arrays as get_occ returns; False: one device uint8 tensor (B, Dx, Dy, Dz), what RayIoU.add_batch and the mIoU histogram
+        take.  With labels (and mask_camera) the 18 x 18 histogram is accumulated into `hist` in the same launch; the result
+        is then (occ, hist, logits) -- as with return_logits -- with None for what was not asked for.  Where the operator
+        does not apply (fused_applies) the module formulation runs and gives today's values."""
+        from . import occ_head, occ_loss
+        if hist is not None and labels is None:
+            raise ValueError('predict_occ: hist needs labels (nothing would be counted)')
+        if self.fused_applies(img_feats):
+            x = self.final_conv(img_feats)
+            lin1, lin2 = self.predicter[0], self.predicter[2]
+            out = occ_head.occ_head_infer(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, dz=self.Dz, labels=labels,
+                                          mask_camera=mask_camera, hist=hist, return_logits=return_logits)
+            pred, hist, logits = out if isinstance(out, tuple) else (out, None, None)
+        else:
+            logits = self.forward(img_feats)
+            if logits.is_cuda and logits.shape[-1] == occ_loss.NUM_CLASSES:
+                pred, h = occ_loss.occ_argmax_hist(logits.float(), labels, mask_camera, hist)
+                pred, hist = pred.view(logits.shape[:-1]), (h if labels is not None else None)
+            else:
+                pred = logits.softmax(-1).argmax(-1).to(torch.uint8)
+                if labels is not None:
+                    t, p = labels.reshape(-1).long(), pred.reshape(-1).long()
+                    keep = t < self.num_classes
+                    if mask_camera is not None:
+                        keep &= mask_camera.reshape(-1).bool()
+                    h = torch.bincount(t[keep] * self.num_classes + p[keep], minlength=self.num_classes ** 2)
+                    h = h.view(self.num_classes, self.num_classes)
+                    hist = h if hist is None else hist.add_(h)
+            logits = logits if return_logits else None
+        occ = list(pred.cpu().numpy()) if to_host else pred
+        if labels is None and not return_logits:
+            return occ
+        return occ, hist, logits
+
     def get_occ(self, occ_pred, img_metas=None):
         from . import occ_loss
         if occ_pred.is_cuda and occ_pred.shape[-1] == occ_loss.NUM_CLASSES:
@@ -689,7 +744,11 @@ class DHD(nn.Module):
 
     def occ_logits(self, img_feats):
         """[x_2d, x_3d] -> voxel logits (B, Dx, Dy, Dz, n_cls): cat -> mix -> occ_head (DHD_model.py:196-198, :224-226)."""
-        return self.occ_head(self._enter('occ_head', self.mix(self._enter('mix', torch.cat(img_feats, dim=1)))))
+        return self.occ_head(self.mixed_feats(img_feats))
+
+    def mixed_feats(self, img_feats):
+        """[x_2d, x_3d] -> the occupancy head's input: cat -> mix, in the head's layout."""
+        return self._enter('occ_head', self.mix(self._enter('mix', torch.cat(img_feats, dim=1))))
 
     def extract_feat(self, points, img_inputs, img_metas=None, **kwargs):
         x_2d, x_3d, depth, height = self.extract_img_feat(img_inputs, img_metas, **kwargs)
@@ -709,7 +768,12 @@ class DHD(nn.Module):
         return self.simple_test_occ([x_2d, x_3d], img_metas)
 
     def simple_test_occ(self, img_feats, img_metas=None):
-        return self.occ_head.get_occ(self.occ_logits(img_feats), img_metas)
+        head = self.occ_head
+        if getattr(head, 'fused_infer', False) and not self.training:
+            # forward-only: final_conv, then one HIP operator down to the class map; where the operator does not apply
+            # predict_occ itself runs get_occ(head(x))
+            return head.predict_occ(self.mixed_feats(img_feats))
+        return head.get_occ(self.occ_logits(img_feats), img_metas)
 
     def flush_bn_counters(self):
         """Add the BatchNorm calls counted on the host since the last flush to the `num_batches_tracked` buffers (one launch).

@@ -733,6 +733,45 @@ int dhd_ray_iou_accumulate(const uint8_t* pred, const uint8_t* gt, int n_samples
                            float voxel_size, int free_id, int n_classes, const float* thresholds, int n_thresholds,
                            int64_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------ *
+ * 14. Occupancy head at inference (models/dense_heads/occ_head.py:84-100,141-153): the predicter MLP
+ *     Linear(c -> hidden) -> Softplus -> Linear(hidden -> dz * n_classes) on every BEV cell of final_conv's output and the
+ *     first-maximum argmax over the classes of every voxel, in one kernel: neither the hidden nor the logits exist in memory.
+ *     Additive to ABI 6.  Supported (dhd_occ_head_infer_supported: 1 / 0): c = 256, hidden = 512, dz = 16, n_classes = 18;
+ *     x float32, float16 or bfloat16 in layout 0 (b, c, dy, dx) or 1 (channels_last: (b, dy, dx, c) in memory), the codes of
+ *     section 10; any b, dy, dx >= 1 with dy * dx <= 2^20.
+ *     Arithmetic: float32 x -- bf16 MFMA on two exact bf16 parts per operand, three products per a*b (DHD_SFA_GEMM_BF16X3 =
+ *     DHD_SFA_GEMM_DEFAULT; other codes unsupported), the float32 hidden split again after Softplus.  Half x -- one f16 / bf16
+ *     MFMA product per a*b with the weights rounded once to that type (gemm must be DHD_SFA_GEMM_DEFAULT); accumulation, bias
+ *     and Softplus (torch's: beta 1, identity above 20) in float32, the hidden rounded to the half type only as the operand of
+ *     the second product, the logits float32.  A NaN in x or in the hidden reaches the logits of its cell, as in torch.
+ * ------------------------------------------------------------------------------------ */
+typedef struct dhd_occ_head_weights {   /* [dev] float32, nn.Linear layout */
+  const float* w1;  /* (hidden, c)             predicter[0].weight */
+  const float* b1;  /* (hidden) */
+  const float* w2;  /* (dz * n_classes, hidden) predicter[2].weight */
+  const float* b2;  /* (dz * n_classes), 16-byte aligned */
+  int32_t c, hidden, dz, n_classes;
+  int32_t gemm;     /* DHD_SFA_GEMM_* */
+} dhd_occ_head_weights;
+
+int dhd_occ_head_infer_supported(int c, int hidden, int dz, int n_classes, int x_dtype, int layout, int gemm);
+
+/* Bytes of `scratch` for one call (a multiple of 16): the weights in the order and number format the kernel consumes them,
+ * rewritten by every call (stale contents do not matter, nothing is kept between calls or process-wide), and behind them the
+ * 18-19 KiB that the kernel's prefetch reads beyond the last weight.  The kernel reads no byte outside these and x. */
+int dhd_occ_head_infer_scratch_bytes(const dhd_occ_head_weights* w, int x_dtype, size_t* bytes);
+
+/* pred [dev] uint8 (b, dx, dy, dz) -- the reference's permute(0, 3, 2, 1); logits [dev] float32 (b, dx, dy, dz, n_classes).
+ * Either may be NULL, not both; pred does not depend on whether logits are stored and equals their first-maximum argmax.
+ * labels / mask [dev] uint8 (b, dx, dy, dz) and hist [dev] int64[n_classes * n_classes], accumulated into, as in
+ * dhd_occ_argmax_hist: hist[t * n_classes + pred] += 1 where t < n_classes and (mask == NULL or mask != 0); all may be NULL,
+ * hist needs labels.  x, scratch, logits and w->b2 16-byte aligned, pred, labels and mask 8-byte aligned.  Every argument
+ * is checked on the host before the first launch; two launches on `stream` (weight stream, then the operator). */
+int dhd_occ_head_infer(const void* x, int x_dtype, int layout, const dhd_occ_head_weights* w, int b, int dy, int dx,
+                       uint8_t* pred, float* logits, const uint8_t* labels, const uint8_t* mask, int64_t* hist,
+                       void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
