@@ -24,6 +24,7 @@
 // and the 16-byte fragment reads (lane = (pixel, k half)) are bank-conflict free (tests/test_host_logic.py simulates both
 // against the bank rules of MI355X_MICROARCH.md).
 #pragma once
+#include "sfa_math.h"
 #include "sfa_mfma.h"
 
 namespace dhd_sfa {
@@ -51,15 +52,14 @@ inline int cu_max_batch(int c, int waves, bool blend = false) {
 }
 
 // EPI 3 (forward-only inference, conv2): the forward epilogue continued through BatchNorm-2, the sigmoid and the final blend
-// out = g*(a*x_bev) + (1-g)*((1-a)*x_voxel), g = sigmoid(sc*y2 + sh) -- the expression of blend2_bn_kernel / blend2_bn_h_kernel
-// (sfa_stage.hip, sfa_stage_half.h) on the 4 (8) pixels of one channel a lane holds after the patch transpose.  y2 is never stored.
+// out = g*(a*x_bev) + (1-g)*((1-a)*x_voxel), g = sigmoid(sc*y2 + sh) -- blend2_bn_kernel's calls into sfa_math.h (sfa_stage.hip)
+// on the 4 (8) pixels of one channel a lane holds after the patch transpose.  y2 is never stored.
 struct CuBlend {
   const void* x;        // (nb, 2C, HW) in the storage type: x_bev | x_voxel of the launch's samples
   const float* a1;      // [nb][C] channel attention
   const float* scsh;    // [2][C] BatchNorm-2 scale | shift
   void* out;            // (nb, C, HW) in the I/O type
 };
-__device__ __forceinline__ float cu_sigmoid(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
 // ReLU pass bits of the cu kernels: one 16-bit word per (tile, 32-row group, staging lane); bit 4*j + e = row 4*g + j of
 // the group, pixel 4*q + e of the tile (lane = 8*g + q): one bit per activation, C 32-bit words per tile.
@@ -405,8 +405,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
           f32x4 r;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float gt = cu_sigmoid(fmaf(sc, o[j], sh));
-            r[j] = gt * (a * pb[j]) + (1.0f - gt) * (na * pv[j]);
+            r[j] = blend_out(blend_gate(sc, o[j], sh), a, na, pb[j], pv[j]);
           }
           const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
               static_cast<TO*>(bl.out) + (size_t)b * C * hw, 0, (unsigned)((size_t)C * hw * sizeof(TO)), 0x00020000);

@@ -16,7 +16,7 @@
 //                       workgroup, swizzled double-buffered LDS tile, ping-pong wave groups, branch-free tile loop), with
 //                       a single operand part -- 64 weight registers per wave instead of 128, one LDS read per MFMA.
 //   pw_wgrad_h_kernel   weight gradients, 64-pixel steps, one 256 x 256 (128 x 128) output tile per CU, per-worker partials.
-//   *_h element-wise passes: 8 elements (16 bytes) per lane and load.
+// The element-wise passes between the GEMMs are sfa_stage.hip's, one set of kernels for every storage type.
 #pragma once
 #include "sfa_gemm_cu.h"
 
@@ -33,14 +33,6 @@ template <> struct HalfOps<_Float16> {
 template <> struct HalfOps<__bf16> {
   static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return mfma_bf16(a, b, c); }
 };
-
-// vector i8 of 8 consecutive elements of TS (16 bytes) <-> 8 floats (widened exactly / rounded to nearest even), streamed
-template <class TS> __device__ __forceinline__ void ld8(const TS* base, size_t i8, float* v) {
-  widen16<TS>(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base) + i8), v);
-}
-template <class TS> __device__ __forceinline__ void st8(TS* base, size_t i8, const float* v) {
-  __builtin_nontemporal_store(narrow16<TS>(v), reinterpret_cast<u32x4*>(base) + i8);
-}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // pw_gemm_cuh_kernel
@@ -285,8 +277,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cuh_kernel(const TS* __
             const f32x2 s2 = Pair<TS>::widen(Pair<TS>::narrow(f32x2{o[2 * i] + bs, o[2 * i + 1] + bs}));
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-              const float gt = cu_sigmoid(fmaf(sc, s2[e], sh));
-              r[2 * i + e] = gt * (a * pb[2 * i + e]) + (1.0f - gt) * (na * pv[2 * i + e]);
+              r[2 * i + e] = blend_out(blend_gate(sc, s2[e], sh), a, na, pb[2 * i + e], pv[2 * i + e]);
             }
           }
           pk = narrow16<TS>(r);
@@ -569,8 +560,7 @@ __global__ __launch_bounds__(kOnePassWaves * 64, 1) void sfa_onepass_h_kernel(co
           const f32x2 s2 = Pair<TS>::widen(Pair<TS>::narrow(f32x2{o[2 * i] + bs, o[2 * i + 1] + bs}));
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
-            const float gt = cu_sigmoid(fmaf(sc, s2[e], sh));
-            r[2 * i + e] = gt * (a * pb[2 * i + e]) + (1.0f - gt) * (na * pv[2 * i + e]);
+            r[2 * i + e] = blend_out(blend_gate(sc, s2[e], sh), a, na, pb[2 * i + e], pv[2 * i + e]);
           }
         }
         store_b128_guarded<0>(narrow16<TS>(r), ry, voff_st, (32 * mt + 8 * k) * row_bytes + p0 * 2);

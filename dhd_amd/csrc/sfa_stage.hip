@@ -29,8 +29,8 @@
 
 #include <type_traits>
 
-#include "sfa_gemm_cu.h"
-#include "sfa_half.h"
+#include "sfa_gemm_cu.h"   // pw_gemm_cu: bf16x3 at C = 128 / 256; brings sfa_math.h (the stage's scalar expressions) and vec16.h
+#include "sfa_half.h"      // pw_gemm_cuh / pw_wgrad_h / sfa_onepass_h: the GEMMs of half storage
 #include "sfa_mfma.h"
 
 using namespace dhd_sfa;
@@ -45,8 +45,6 @@ constexpr int kWgBlock = 512;     // pw_wgrad: 8 waves
 constexpr int kWgStride = 33;     // LDS row stride of a 32-pixel operand row (conflict-free column reads)
 constexpr int kWgWorkers = 256;   // total pw_wgrad blocks (one per CU)
 
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
-
 __device__ __forceinline__ float block_sum(float v, float* sm) {
   v = group_sum(v, DHD_WAVE);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -58,37 +56,132 @@ __device__ __forceinline__ float block_sum(float v, float* sm) {
   return t;
 }
 
-// [lo, hi) in float4 units of this block's share of a plane of hw floats (hw % 4 == 0).
-__device__ __forceinline__ void chunk_range4(int hw, int* lo, int* hi) {
-  const int n4 = hw >> 2, per = (n4 + kPlaneChunks - 1) / kPlaneChunks;
+// ------------------------------------------------------------------------------------------------
+// element-wise passes: one kernel per pass for every storage type TS (float, _Float16, __bf16)
+// ------------------------------------------------------------------------------------------------
+// A lane handles N = kVec16<TS> consecutive elements per vector: 16 bytes of the storage tensors (x, y1, y2, g2, g1, du), the
+// same N elements of the I/O tensors (out, gout, gx; IoVec below).  float32 arithmetic, sfa_math.h's expressions.
+//
+// The storage types differ in THREE respects and nowhere else.  Each was a measured choice for its type; changing one is a
+// performance change with a measurement of its own.
+template <class TS> constexpr bool kHalfStorage = !std::is_same_v<TS, float>;
+// 1. Cache policy.  Half storage streams every tensor non-temporally.  float32 storage leaves five accesses plain: the read of
+//    y2 in blend2_bn and blend2_bn_bwd, the read of du in blend1_da, the store of g2, and both reads of pair_sums' tail iteration
+//    (its main loop is non-temporal: 62 -> 52 us); everything else is non-temporal there too.
+template <class TS> constexpr bool kStreamAll = kHalfStorage<TS>;
+// 2. Vectors in flight per thread and stream in blend2_bn_bwd and stage_gx: two under half storage, one under float32 storage.
+//    (plane_mean and pair_sums keep two, blend2_bn and blend1_da one, whatever the type.)
+template <class TS> constexpr int kWideInFlight = kHalfStorage<TS> ? 2 : 1;
+// 3. In-lane fold of the reductions in pair_sums and blend1_da: float32 storage sums a vector pairwise, (a+b)+(c+d), with plain
+//    multiplies; half storage runs an fmaf chain over its eight elements (fold_sum, fold_dot below).
+template <class TS> constexpr bool kFoldPairwise = !kHalfStorage<TS>;
+
+// [lo, hi) in N-element vectors of this block's share of a plane of hw elements (hw % N == 0).
+template <int N> __device__ __forceinline__ void chunk_range(int hw, int* lo, int* hi) {
+  static_assert(N == 4 || N == 8, "16 bytes of float32 or of a half type");
+  const int n = hw >> (N == 8 ? 3 : 2), per = (n + kPlaneChunks - 1) / kPlaneChunks;
   *lo = blockIdx.x * per;
-  *hi = min(n4, *lo + per);
+  *hi = min(n, *lo + per);
+}
+
+// Vector i of N consecutive elements of an I/O tensor (dhd_sfa_weights.io_dtype) as float32, non-temporal: 16 bytes when the
+// element is as wide as the storage type's, 8 bytes of a half type beside float32 storage (N = 4).  Widened exactly / rounded
+// to nearest even; the 8-byte store converts element by element (vec16.h: the pairwise form is another instruction order).
+template <class TO, int N> struct IoVec {
+  static constexpr bool k16 = N == kVec16<TO>;
+  static_assert(k16 || (N == 4 && sizeof(TO) == 2), "16 bytes, or four elements of a half type");
+  using raw = std::conditional_t<k16, raw16<TO>, u32x2>;
+  static __device__ __forceinline__ raw ld(const TO* base, size_t i) { return __builtin_nontemporal_load(reinterpret_cast<const raw*>(base) + i); }
+  static __device__ __forceinline__ void widen(raw w, float* v) {
+    if constexpr (k16) {
+      widen16<TO>(w, v);
+    } else {
+      const f32x2 a = Pair<TO>::widen(w.x), b = Pair<TO>::widen(w.y);
+      v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
+    }
+  }
+  static __device__ __forceinline__ void store(TO* base, size_t i, const float* v) {
+    if constexpr (k16) {
+      Vec16<TO, true>::store(base, i, v);
+    } else {
+      typedef TO t4 __attribute__((ext_vector_type(4)));
+      const t4 h = {(TO)v[0], (TO)v[1], (TO)v[2], (TO)v[3]};
+      __builtin_nontemporal_store(h, reinterpret_cast<t4*>(base) + i);
+    }
+  }
+};
+
+// sum of a vector's elements as a pairwise tree: (v0+v1)+(v2+v3), and for eight ((v0+v1)+(v2+v3))+((v4+v5)+(v6+v7))
+template <int N> __device__ __forceinline__ float tree_sum(const float* v) {
+  if constexpr (N == 4) return (v[0] + v[1]) + (v[2] + v[3]);
+  else return tree_sum<N / 2>(v) + tree_sum<N / 2>(v + N / 2);
+}
+
+// acc + sum_j a[j]  and  acc + sum_j a[j]*d(j)  over one vector, in the storage type's order (kFoldPairwise)
+template <class TS> __device__ __forceinline__ float fold_sum(float acc, const float* a) {
+  if constexpr (kFoldPairwise<TS>) return acc + tree_sum<kVec16<TS>>(a);
+#pragma unroll
+  for (int j = 0; j < kVec16<TS>; ++j) acc += a[j];
+  return acc;
+}
+template <class TS, class D> __device__ __forceinline__ float fold_dot(float acc, const float* a, D d) {
+  if constexpr (kFoldPairwise<TS>) {
+    static_assert(kVec16<TS> == 4, "the pairwise fold is written for four elements");
+    return acc + ((a[0] * d(0) + a[1] * d(1)) + (a[2] * d(2) + a[3] * d(3)));
+  }
+#pragma unroll
+  for (int j = 0; j < kVec16<TS>; ++j) acc = fmaf(a[j], d(j), acc);
+  return acc;
+}
+
+// A thread's vectors lo + threadIdx.x, + kEwBlock, ... below hi: body(load(i), i) for each, with the loads of K (1 or 2) vectors
+// requested before the first of them is used.
+template <int K, class Load, class Body> __device__ __forceinline__ void for_each_vector(int lo, int hi, Load load, Body body) {
+  int i = lo + threadIdx.x;
+  if constexpr (K == 2) {
+    for (; i + kEwBlock < hi; i += 2 * kEwBlock) {
+      const auto u = load(i), w = load(i + kEwBlock);
+      body(u, i);
+      body(w, i + kEwBlock);
+    }
+    if (i < hi) body(load(i), i);
+  } else {
+    for (; i < hi; i += kEwBlock) body(load(i), i);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
 // small dense pieces: channel mean -> fc -> a, and its backward
 // ------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ void plane_mean_block(const float* __restrict__ x, float* __restrict__ part, int hw, float* sm) {
+// channel means of x: a block's share of plane blockIdx.y
+template <class TS>
+__device__ __forceinline__ void plane_mean_block(const TS* __restrict__ x, float* __restrict__ part, int hw, float* sm) {
+  constexpr int N = kVec16<TS>;
+  using X = Vec16<TS, true>;
   const size_t plane = blockIdx.y;
-  const f32x4* p4 = reinterpret_cast<const f32x4*>(x + plane * hw);
+  const TS* p = x + plane * hw;
   int lo, hi;
-  chunk_range4(hw, &lo, &hi);
+  chunk_range<N>(hw, &lo, &hi);
   float a0 = 0.f, a1 = 0.f;
   int i = lo + threadIdx.x;
   for (; i + kEwBlock < hi; i += 2 * kEwBlock) {
-    f32x4 v = __builtin_nontemporal_load(p4 + i), w = __builtin_nontemporal_load(p4 + i + kEwBlock);
-    a0 += (v.x + v.y) + (v.z + v.w);
-    a1 += (w.x + w.y) + (w.z + w.w);
+    float v[N], w[N];
+    X::load(p, i, v);
+    X::load(p, (size_t)i + kEwBlock, w);
+    a0 += tree_sum<N>(v);
+    a1 += tree_sum<N>(w);
   }
   if (i < hi) {
-    f32x4 v = __builtin_nontemporal_load(p4 + i);
-    a0 += (v.x + v.y) + (v.z + v.w);
+    float v[N];
+    X::load(p, i, v);
+    a0 += tree_sum<N>(v);
   }
-  float tot = block_sum(a0 + a1, sm);
+  const float tot = block_sum(a0 + a1, sm);
   if (threadIdx.x == 0) part[plane * kPlaneChunks + blockIdx.x] = tot;
 }
 
+// the mean-only launch of the plans that pack their weight images in launches of their own (streamed / f32: float32 storage)
 __global__ __launch_bounds__(kEwBlock) void plane_mean_kernel(const float* __restrict__ x, float* __restrict__ part, int hw) {
   __shared__ float sm[kEwBlock / DHD_WAVE];
   plane_mean_block(x, part, hw, sm);
@@ -285,7 +378,7 @@ __global__ __launch_bounds__(kEwBlock) void moments_kernel(const float* __restri
   const float k = y[(size_t)ch * hw];
   const f32x4* p4 = reinterpret_cast<const f32x4*>(y + (size_t)plane * hw);
   int lo, hi;
-  chunk_range4(hw, &lo, &hi);
+  chunk_range<4>(hw, &lo, &hi);
   float s1 = 0.f, s2 = 0.f;
   for (int i = lo + threadIdx.x; i < hi; i += kEwBlock) {
     f32x4 v = p4[i];
@@ -505,154 +598,173 @@ __device__ __forceinline__ void bn_backward_publish(const BnTail& t, float* __re
 }
 
 // sums for BatchNorm backward: S1 = sum g, S2 = sum g*(y - mean).  part: [(b*chunks+chunk)][2][c]
-__global__ __launch_bounds__(kEwBlock) void pair_sums_kernel(const float* __restrict__ g, const float* __restrict__ y,
+template <class TS>
+__global__ __launch_bounds__(kEwBlock) void pair_sums_kernel(const TS* __restrict__ g, const TS* __restrict__ y,
                                                              const float* __restrict__ mean, float* __restrict__ part, int c, int hw,
                                                              BnTail tail) {
+  constexpr int N = kVec16<TS>;
+  using Main = Vec16<TS, true>;              // streamed once here
+  using Tail = Vec16<TS, kStreamAll<TS>>;
   __shared__ float sm[kEwBlock / DHD_WAVE];
   const int plane = blockIdx.y, b = plane / c, ch = plane % c;
   const float mu = mean[ch];
-  const f32x4* g4 = reinterpret_cast<const f32x4*>(g + (size_t)plane * hw);
-  const f32x4* y4 = reinterpret_cast<const f32x4*>(y + (size_t)plane * hw);
+  const TS* gp = g + (size_t)plane * hw;
+  const TS* yp = y + (size_t)plane * hw;
   int lo, hi;
-  chunk_range4(hw, &lo, &hi);
+  chunk_range<N>(hw, &lo, &hi);
   float s1 = 0.f, s2 = 0.f, t1 = 0.f, t2 = 0.f;
   int i = lo + threadIdx.x;
-  for (; i + kEwBlock < hi; i += 2 * kEwBlock) {  // two independent 16-byte streams per thread
-    // streamed once here: non-temporal, like plane_mean (62 -> 52 us)
-    f32x4 a = __builtin_nontemporal_load(g4 + i), v = __builtin_nontemporal_load(y4 + i), a2 = __builtin_nontemporal_load(g4 + i + kEwBlock),
-          v2 = __builtin_nontemporal_load(y4 + i + kEwBlock);
-    s1 += (a.x + a.y) + (a.z + a.w);
-    s2 += (a.x * (v.x - mu) + a.y * (v.y - mu)) + (a.z * (v.z - mu) + a.w * (v.w - mu));
-    t1 += (a2.x + a2.y) + (a2.z + a2.w);
-    t2 += (a2.x * (v2.x - mu) + a2.y * (v2.y - mu)) + (a2.z * (v2.z - mu) + a2.w * (v2.w - mu));
+  for (; i + kEwBlock < hi; i += 2 * kEwBlock) {   // two independent 16-byte vectors of either stream per thread
+    float a[N], v[N], a2[N], v2[N];
+    Main::load(gp, i, a);
+    Main::load(yp, i, v);
+    Main::load(gp, (size_t)i + kEwBlock, a2);
+    Main::load(yp, (size_t)i + kEwBlock, v2);
+    s1 = fold_sum<TS>(s1, a);
+    s2 = fold_dot<TS>(s2, a, [&](int j) { return v[j] - mu; });
+    t1 = fold_sum<TS>(t1, a2);
+    t2 = fold_dot<TS>(t2, a2, [&](int j) { return v2[j] - mu; });
   }
   if (i < hi) {
-    f32x4 a = g4[i], v = y4[i];
-    s1 += (a.x + a.y) + (a.z + a.w);
-    s2 += (a.x * (v.x - mu) + a.y * (v.y - mu)) + (a.z * (v.z - mu) + a.w * (v.w - mu));
+    float a[N], v[N];
+    Tail::load(gp, i, a);
+    Tail::load(yp, i, v);
+    s1 = fold_sum<TS>(s1, a);
+    s2 = fold_dot<TS>(s2, a, [&](int j) { return v[j] - mu; });
   }
-  s1 += t1;
-  s2 += t2;
-  s1 = block_sum(s1, sm);
-  s2 = block_sum(s2, sm);
-  if (threadIdx.x == 0) {
-    bn_backward_publish(tail, part, (size_t)(b * kPlaneChunks + blockIdx.x), ch, c, s1, s2);
-  }
+  s1 = block_sum(s1 + t1, sm);
+  s2 = block_sum(s2 + t2, sm);
+  if (threadIdx.x == 0) bn_backward_publish(tail, part, (size_t)(b * kPlaneChunks + blockIdx.x), ch, c, s1, s2);
 }
 
 // ------------------------------------------------------------------------------------------------
 // fused blends
 // ------------------------------------------------------------------------------------------------
 
-// Four consecutive elements of the stage's edge tensors (out, gout, gx: dhd_sfa_weights.io_dtype) as float32: 16 bytes of
-// float32, 8 bytes of a half type (widened exactly / rounded to nearest even).
-template <class T> __device__ __forceinline__ f32x4 ld4(const T* base, size_t i4) {
-  if constexpr (std::is_same_v<T, float>) {
-    return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base) + i4);
-  } else {
-    const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(base) + i4);
-    const f32x2 a = Pair<T>::widen(w.x), b = Pair<T>::widen(w.y);
-    return f32x4{a.x, a.y, b.x, b.y};
-  }
-}
-// element-wise converts: the pairwise Pair<T>::narrow gives the same instructions in another order
-template <class T> __device__ __forceinline__ void st4(T* base, size_t i4, f32x4 v) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  const t4 h = {(T)v.x, (T)v.y, (T)v.z, (T)v.w};
-  __builtin_nontemporal_store(h, reinterpret_cast<t4*>(base) + i4);
-}
-
 // out = g*(a*xb) + (1-g)*((1-a)*xv),  g = sigmoid(sc*y2 + sh)
-template <class TO>
-__global__ __launch_bounds__(kEwBlock) void blend2_bn_kernel(const float* __restrict__ x, const float* __restrict__ a1,
-                                                             const float* __restrict__ y2, const float* __restrict__ scsh,
+template <class TS, class TO>
+__global__ __launch_bounds__(kEwBlock) void blend2_bn_kernel(const TS* __restrict__ x, const float* __restrict__ a1,
+                                                             const TS* __restrict__ y2, const float* __restrict__ scsh,
                                                              TO* __restrict__ out, int c, int hw) {
+  constexpr int N = kVec16<TS>;
+  using X = Vec16<TS, true>;
+  using Y2 = Vec16<TS, kStreamAll<TS>>;
   const int plane = blockIdx.y, b = plane / c, ch = plane % c;
   const float a = a1[plane], na = 1.0f - a, sc = scsh[ch], sh = scsh[c + ch];
-  const f32x4* b4 = reinterpret_cast<const f32x4*>(x + ((size_t)b * 2 * c + ch) * hw);
-  const f32x4* v4 = reinterpret_cast<const f32x4*>(x + ((size_t)b * 2 * c + c + ch) * hw);
-  const f32x4* y4 = reinterpret_cast<const f32x4*>(y2 + (size_t)plane * hw);
-  TO* o4 = out + (size_t)plane * hw;
+  const TS* xb = x + ((size_t)b * 2 * c + ch) * hw;
+  const TS* xv = x + ((size_t)b * 2 * c + c + ch) * hw;
+  const TS* yp = y2 + (size_t)plane * hw;
+  TO* op = out + (size_t)plane * hw;
   int lo, hi;
-  chunk_range4(hw, &lo, &hi);
+  chunk_range<N>(hw, &lo, &hi);
   for (int i = lo + threadIdx.x; i < hi; i += kEwBlock) {
-    f32x4 p = __builtin_nontemporal_load(b4 + i), q = __builtin_nontemporal_load(v4 + i), s = y4[i], r;
+    float p[N], q[N], s[N], r[N];
+    X::load(xb, i, p);
+    X::load(xv, i, q);
+    Y2::load(yp, i, s);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float g = sigmoidf_(fmaf(sc, s[j], sh));
-      r[j] = g * (a * p[j]) + (1.0f - g) * (na * q[j]);
-    }
-    st4<TO>(o4, i, r);
+    for (int j = 0; j < N; ++j) r[j] = blend_out(blend_gate(sc, s[j], sh), a, na, p[j], q[j]);
+    IoVec<TO, N>::store(op, i, r);
   }
 }
 
-// g2 = dL/d s2 = go*(a*xb - (1-a)*xv)*g*(1-g); sums for BatchNorm-2 backward; the go-part of dL/da:
-// sum go*(g*xb - (1-g)*xv).   part: [(b*chunks+chunk)][2][c];  da_p1: [(b*chunks+chunk)][c]
-template <class TO>
-__global__ __launch_bounds__(kEwBlock) void blend2_bn_bwd_kernel(const float* __restrict__ x, const float* __restrict__ a1,
-                                                                 const float* __restrict__ y2, const float* __restrict__ scsh,
+// g2 = dL/d s2 = go*(a*xb - (1-a)*xv)*g*(1-g), stored in TS; the BatchNorm-2 backward sums are those of the STORED g2 (float32
+// storage: the value itself); the go-part of dL/da: sum go*(g*xb - (1-g)*xv).
+// part: [(b*chunks+chunk)][2][c];  da_p1: [(b*chunks+chunk)][c]
+template <class TS, class TO>
+__global__ __launch_bounds__(kEwBlock) void blend2_bn_bwd_kernel(const TS* __restrict__ x, const float* __restrict__ a1,
+                                                                 const TS* __restrict__ y2, const float* __restrict__ scsh,
                                                                  const float* __restrict__ mean, const TO* __restrict__ go,
-                                                                 float* __restrict__ g2, float* __restrict__ part,
+                                                                 TS* __restrict__ g2, float* __restrict__ part,
                                                                  float* __restrict__ da_p1, int c, int hw, BnTail tail) {
+  constexpr int N = kVec16<TS>;
+  using X = Vec16<TS, true>;
+  using Y2 = Vec16<TS, kStreamAll<TS>>;
+  using G2 = Vec16<TS, kStreamAll<TS>>;
+  using Go = IoVec<TO, N>;
   __shared__ float sm[kEwBlock / DHD_WAVE];
   const int plane = blockIdx.y, b = plane / c, ch = plane % c;
   const float a = a1[plane], na = 1.0f - a, sc = scsh[ch], sh = scsh[c + ch], mu = mean[ch];
-  const f32x4* b4 = reinterpret_cast<const f32x4*>(x + ((size_t)b * 2 * c + ch) * hw);
-  const f32x4* v4 = reinterpret_cast<const f32x4*>(x + ((size_t)b * 2 * c + c + ch) * hw);
-  const f32x4* y4 = reinterpret_cast<const f32x4*>(y2 + (size_t)plane * hw);
-  const TO* o4 = go + (size_t)plane * hw;
-  f32x4* r4 = reinterpret_cast<f32x4*>(g2 + (size_t)plane * hw);
+  const TS* xb = x + ((size_t)b * 2 * c + ch) * hw;
+  const TS* xv = x + ((size_t)b * 2 * c + c + ch) * hw;
+  const TS* yp = y2 + (size_t)plane * hw;
+  const TO* gp = go + (size_t)plane * hw;
+  TS* rp = g2 + (size_t)plane * hw;
   int lo, hi;
-  chunk_range4(hw, &lo, &hi);
+  chunk_range<N>(hw, &lo, &hi);
   float s1 = 0.f, s2 = 0.f, sa = 0.f;
-  for (int i = lo + threadIdx.x; i < hi; i += kEwBlock) {
-    f32x4 p = __builtin_nontemporal_load(b4 + i), q = __builtin_nontemporal_load(v4 + i), s = y4[i], o = ld4<TO>(o4, i), r;
+  struct In {
+    raw16<TS> p, q, s;
+    typename Go::raw o;
+  };
+  auto load = [&](int i) { return In{X::ld(xb, i), X::ld(xv, i), Y2::ld(yp, i), Go::ld(gp, i)}; };
+  auto body = [&](const In& in, int i) {
+    float p[N], q[N], s[N], o[N], r[N];
+    widen16<TS>(in.p, p);
+    widen16<TS>(in.q, q);
+    widen16<TS>(in.s, s);
+    Go::widen(in.o, o);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float g = sigmoidf_(fmaf(sc, s[j], sh));
-      const float v = o[j] * (a * p[j] - na * q[j]) * g * (1.0f - g);
-      r[j] = v;
-      s1 += v;
-      s2 = fmaf(v, s[j] - mu, s2);
-      sa = fmaf(o[j], g * p[j] - (1.0f - g) * q[j], sa);
+    for (int j = 0; j < N; ++j) {
+      const float g = blend_gate(sc, s[j], sh);
+      r[j] = blend_gate_grad(o[j], g, a, na, p[j], q[j]);
+      sa = blend_da_add(sa, o[j], g, p[j], q[j]);
     }
-    r4[i] = r;
-  }
+    const raw16<TS> pk = narrow16<TS>(r);
+    G2::st(rp, i, pk);
+    widen16<TS>(pk, r);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      s1 += r[j];
+      s2 = fmaf(r[j], s[j] - mu, s2);
+    }
+  };
+  for_each_vector<kWideInFlight<TS>>(lo, hi, load, body);
   s1 = block_sum(s1, sm);
   s2 = block_sum(s2, sm);
   sa = block_sum(sa, sm);
   if (threadIdx.x == 0) {
-    const size_t q = (size_t)(b * kPlaneChunks + blockIdx.x);
-    da_p1[q * c + ch] = sa;
-    bn_backward_publish(tail, part, q, ch, c, s1, s2);
+    const size_t qi = (size_t)(b * kPlaneChunks + blockIdx.x);
+    da_p1[qi * c + ch] = sa;
+    bn_backward_publish(tail, part, qi, ch, c, s1, s2);
   }
 }
 
 // the du-part of dL/da: sum du*(xb - xv).   da_p2: [(b*chunks+chunk)][c]
-__global__ __launch_bounds__(kEwBlock) void blend1_da_kernel(const float* __restrict__ x, const float* __restrict__ du,
+template <class TS>
+__global__ __launch_bounds__(kEwBlock) void blend1_da_kernel(const TS* __restrict__ x, const TS* __restrict__ du,
                                                              float* __restrict__ da_p2, int c, int hw) {
+  constexpr int N = kVec16<TS>;
+  using X = Vec16<TS, true>;
+  using Du = Vec16<TS, kStreamAll<TS>>;
   __shared__ float sm[kEwBlock / DHD_WAVE];
   const int plane = blockIdx.y, b = plane / c, ch = plane % c;
-  const f32x4* b4 = reinterpret_cast<const f32x4*>(x + ((size_t)b * 2 * c + ch) * hw);
-  const f32x4* v4 = reinterpret_cast<const f32x4*>(x + ((size_t)b * 2 * c + c + ch) * hw);
-  const f32x4* d4 = reinterpret_cast<const f32x4*>(du + (size_t)plane * hw);
+  const TS* xb = x + ((size_t)b * 2 * c + ch) * hw;
+  const TS* xv = x + ((size_t)b * 2 * c + c + ch) * hw;
+  const TS* dp = du + (size_t)plane * hw;
   int lo, hi;
-  chunk_range4(hw, &lo, &hi);
+  chunk_range<N>(hw, &lo, &hi);
   float acc = 0.f;
   for (int i = lo + threadIdx.x; i < hi; i += kEwBlock) {
-    f32x4 p = __builtin_nontemporal_load(b4 + i), q = __builtin_nontemporal_load(v4 + i), d = d4[i];
-    acc += (d.x * (p.x - q.x) + d.y * (p.y - q.y)) + (d.z * (p.z - q.z) + d.w * (p.w - q.w));
+    float p[N], q[N], d[N];
+    X::load(xb, i, p);
+    X::load(xv, i, q);
+    Du::load(dp, i, d);
+    acc = fold_dot<TS>(acc, d, [&](int j) { return p[j] - q[j]; });
   }
   acc = block_sum(acc, sm);
   if (threadIdx.x == 0) da_p2[(size_t)(b * kPlaneChunks + blockIdx.x) * c + ch] = acc;
 }
 
 // gx_bev = a*(go*g + du) + ds_bev/hw;  gx_vox = (1-a)*(go*(1-g) + du) + ds_vox/hw
-template <class TO>
-__global__ __launch_bounds__(kEwBlock) void stage_gx_kernel(const float* __restrict__ a1, const float* __restrict__ y2,
+template <class TS, class TO>
+__global__ __launch_bounds__(kEwBlock) void stage_gx_kernel(const float* __restrict__ a1, const TS* __restrict__ y2,
                                                             const float* __restrict__ scsh, const TO* __restrict__ go,
-                                                            const float* __restrict__ du, const float* __restrict__ ds,
+                                                            const TS* __restrict__ du, const float* __restrict__ ds,
                                                             TO* __restrict__ gx, int c, int hw, int fc_rows, FcGradJob fc) {
+  constexpr int N = kVec16<TS>;
+  using S = Vec16<TS, true>;
+  using Io = IoVec<TO, N>;
   if ((int)blockIdx.y < fc_rows) {   // the first block rows: the Linear layers' parameter gradients (dispatched first, no tail)
     fc_param_grad_block(fc, (int)blockIdx.y * kPlaneChunks + (int)blockIdx.x, c);
     return;
@@ -660,24 +772,34 @@ __global__ __launch_bounds__(kEwBlock) void stage_gx_kernel(const float* __restr
   const int plane = (int)blockIdx.y - fc_rows, b = plane / c, ch = plane % c;
   const float a = a1[plane], na = 1.0f - a, sc = scsh[ch], sh = scsh[c + ch];
   const float kb = ds[(size_t)b * 2 * c + ch] / (float)hw, kv = ds[(size_t)b * 2 * c + c + ch] / (float)hw;
-  const f32x4* y4 = reinterpret_cast<const f32x4*>(y2 + (size_t)plane * hw);
-  const TO* o4 = go + (size_t)plane * hw;
-  const f32x4* d4 = reinterpret_cast<const f32x4*>(du + (size_t)plane * hw);
-  TO* gb4 = gx + ((size_t)b * 2 * c + ch) * hw;
-  TO* gv4 = gx + ((size_t)b * 2 * c + c + ch) * hw;
+  const TS* yp = y2 + (size_t)plane * hw;
+  const TO* gp = go + (size_t)plane * hw;
+  const TS* dp = du + (size_t)plane * hw;
+  TO* gb = gx + ((size_t)b * 2 * c + ch) * hw;
+  TO* gv = gx + ((size_t)b * 2 * c + c + ch) * hw;
   int lo, hi;
-  chunk_range4(hw, &lo, &hi);
-  for (int i = lo + threadIdx.x; i < hi; i += kEwBlock) {
-    f32x4 s = __builtin_nontemporal_load(y4 + i), o = ld4<TO>(o4, i), d = __builtin_nontemporal_load(d4 + i), rb, rv;
+  chunk_range<N>(hw, &lo, &hi);
+  struct In {
+    raw16<TS> s;
+    typename Io::raw o;
+    raw16<TS> d;
+  };
+  auto load = [&](int i) { return In{S::ld(yp, i), Io::ld(gp, i), S::ld(dp, i)}; };
+  auto body = [&](const In& in, int i) {
+    float s[N], o[N], d[N], rb[N], rv[N];
+    widen16<TS>(in.s, s);
+    Io::widen(in.o, o);
+    widen16<TS>(in.d, d);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float g = sigmoidf_(fmaf(sc, s[j], sh));
-      rb[j] = fmaf(a, fmaf(o[j], g, d[j]), kb);
-      rv[j] = fmaf(na, fmaf(o[j], 1.0f - g, d[j]), kv);
+    for (int j = 0; j < N; ++j) {
+      const float g = blend_gate(sc, s[j], sh);
+      rb[j] = stage_gx_bev(a, o[j], g, d[j], kb);
+      rv[j] = stage_gx_vox(na, o[j], g, d[j], kv);
     }
-    st4<TO>(gb4, i, rb);
-    st4<TO>(gv4, i, rv);
-  }
+    Io::store(gb, i, rb);
+    Io::store(gv, i, rv);
+  };
+  for_each_vector<kWideInFlight<TS>>(lo, hi, load, body);
 }
 
 #include "sfa_gemm_streamed.h"   // pw_gemm / pw_gemm6 / pw_wgrad / pw_wgrad6: the f32 reference point and bf16x6 at C = 512
@@ -690,17 +812,21 @@ struct PackJob {
   const float* w[2];     // conv1, conv2
   u32x4* dst[4];         // conv1, conv2, conv1^T, conv2^T
   int c, cob, nt, blocks_each;
-  int cu;                // images for pw_gemm_cu_kernel (sfa_gemm_cu.h: A fragments, one 32-channel tile after the other)
+  int cu;                // images for pw_gemm_cu_kernel (sfa_gemm_cu.h: A fragments, one 32-channel tile after the other), else
+                         // for pw_gemm_res (cob, nt).  float32 storage only: half storage has one kind of image, cuh_pack_weight
 };
 
-__global__ __launch_bounds__(kEwBlock) void plane_mean_pack_kernel(const float* __restrict__ x, float* __restrict__ part, int hw,
+template <class TS>
+__global__ __launch_bounds__(kEwBlock) void plane_mean_pack_kernel(const TS* __restrict__ x, float* __restrict__ part, int hw,
                                                                    int n_planes, PackJob job) {
   __shared__ float sm[kEwBlock / DHD_WAVE];
   if ((int)blockIdx.y < n_planes) { plane_mean_block(x, part, hw, sm); return; }
   const int pb = ((int)blockIdx.y - n_planes) * kPlaneChunks + (int)blockIdx.x;
   const int which = pb / job.blocks_each;
   if (which >= 4 || job.dst[which] == nullptr) return;   // (forward-only inference packs no transposes)
-  if (job.cu) cu_pack_weight(job.w[which & 1], which >> 1, job.dst[which], job.c, (pb % job.blocks_each) * kEwBlock + (int)threadIdx.x);
+  if constexpr (kHalfStorage<TS>)
+    cuh_pack_weight<TS>(job.w[which & 1], which >> 1, job.dst[which], job.c, (pb % job.blocks_each) * kEwBlock + (int)threadIdx.x);
+  else if (job.cu) cu_pack_weight(job.w[which & 1], which >> 1, job.dst[which], job.c, (pb % job.blocks_each) * kEwBlock + (int)threadIdx.x);
   else pack_weight_res_block(job.w[which & 1], which >> 1, job.dst[which], job.c, job.cob, job.nt, pb % job.blocks_each);
 }
 
@@ -1006,8 +1132,6 @@ __global__ __launch_bounds__(kEwBlock) void wgrad_reduce_kernel(const float* __r
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-
-#include "sfa_stage_half.h"   // the element-wise kernels of the half-storage form
 
 constexpr int kTickWords = 64;                     // arrival counters besides the per-channel ones (see saved_layout)
 constexpr int kResWaves = 8;                       // waves per resident workgroup
@@ -1461,67 +1585,37 @@ int launch_wgrad(const Plan& p, Op b_of, const TS* a0, const TS* a1, const float
 
 // The channel means of x and the four weight images of a call: conv1 and conv2 (scratch), their transposes for the data
 // gradients (saved).  dst: conv1, conv2, conv1^T, conv2^T.
-int launch_mean_pack(const Plan& p, const float* x, const float* w1, const float* w2, void* const dst[4], float* mean_part, int b,
+template <class TS>
+int launch_mean_pack(const Plan& p, const TS* x, const float* w1, const float* w2, void* const dst[4], float* mean_part, int b,
                      int c, int hw, hipStream_t st) {
   const int blocks_each = dhd_cdiv((c / 32) * (c / 16) * 64, kEwBlock);
-  if (p.pack == Pack::cu || p.pack == Pack::res) {   // one launch: the images in rows of extra blocks
+  if (p.pack == Pack::cu || p.pack == Pack::res || p.pack == Pack::cuh) {   // one launch: the images in rows of extra blocks
     PackJob job;
     job.w[0] = w1; job.w[1] = w2;
     for (int i = 0; i < 4; ++i) job.dst[i] = static_cast<u32x4*>(dst[i]);
     job.c = c; job.nt = p.nt; job.cob = p.cob; job.cu = p.pack == Pack::cu ? 1 : 0;
     job.blocks_each = blocks_each;
     const dim3 grid(kPlaneChunks, b * 2 * c + dhd_cdiv(4 * blocks_each, kPlaneChunks));
-    hipLaunchKernelGGL(plane_mean_pack_kernel, grid, dim3(kEwBlock), 0, st, x, mean_part, hw, b * 2 * c, job);
+    hipLaunchKernelGGL(plane_mean_pack_kernel<TS>, grid, dim3(kEwBlock), 0, st, x, mean_part, hw, b * 2 * c, job);
     DHD_LAUNCH_CHECK();
     return DHD_OK;
   }
-  hipLaunchKernelGGL(plane_mean_kernel, dim3(kPlaneChunks, b * 2 * c), dim3(kEwBlock), 0, st, x, mean_part, hw);
-  DHD_LAUNCH_CHECK();
-  for (int i = 0; i < 4; ++i) {   // the streamed / f32 forms pack one weight per launch
-    const float* wi = i & 1 ? w2 : w1;
-    if (p.pack == Pack::six)
-      hipLaunchKernelGGL(pack_weight6_kernel, dim3(blocks_each), dim3(kEwBlock), 0, st, wi, i >> 1, static_cast<u32x4*>(dst[i]), c, p.cot);
-    else
-      hipLaunchKernelGGL(pack_weight_kernel, dim3(dhd_cdiv(c * c, kEwBlock)), dim3(kEwBlock), 0, st, wi, i >> 1, static_cast<float*>(dst[i]),
-                         c, p.cot);
+  if constexpr (std::is_same_v<TS, float>) {
+    hipLaunchKernelGGL(plane_mean_kernel, dim3(kPlaneChunks, b * 2 * c), dim3(kEwBlock), 0, st, x, mean_part, hw);
     DHD_LAUNCH_CHECK();
+    for (int i = 0; i < 4; ++i) {   // the streamed / f32 forms pack one weight per launch
+      const float* wi = i & 1 ? w2 : w1;
+      if (p.pack == Pack::six)
+        hipLaunchKernelGGL(pack_weight6_kernel, dim3(blocks_each), dim3(kEwBlock), 0, st, wi, i >> 1, static_cast<u32x4*>(dst[i]), c, p.cot);
+      else
+        hipLaunchKernelGGL(pack_weight_kernel, dim3(dhd_cdiv(c * c, kEwBlock)), dim3(kEwBlock), 0, st, wi, i >> 1, static_cast<float*>(dst[i]),
+                           c, p.cot);
+      DHD_LAUNCH_CHECK();
+    }
+    return DHD_OK;
   }
-  return DHD_OK;
+  return DHD_EINVAL;   // (make_plan gives half storage Pack::cuh)
 }
-template <class TS>
-int launch_mean_pack(const Plan&, const TS* x, const float* w1, const float* w2, void* const dst[4], float* mean_part, int b, int c,
-                     int hw, hipStream_t st) {
-  PackJobH job;
-  job.w[0] = w1; job.w[1] = w2;
-  for (int i = 0; i < 4; ++i) job.dst[i] = static_cast<u32x4*>(dst[i]);
-  job.c = c;
-  job.blocks_each = dhd_cdiv((c / 32) * (c / 16) * 64, kEwBlock);
-  const dim3 grid(kPlaneChunks, b * 2 * c + dhd_cdiv(4 * job.blocks_each, kPlaneChunks));
-  hipLaunchKernelGGL(plane_mean_pack_h_kernel<TS>, grid, dim3(kEwBlock), 0, st, x, mean_part, hw, b * 2 * c, job);
-  DHD_LAUNCH_CHECK();
-  return DHD_OK;
-}
-
-// The element-wise kernels that read or write tensors of the storage type TS, or the I/O tensors (out, gout, gx) of type TO:
-// half storage (TO == TS) ...
-template <class TS, class TO>
-struct Ew {
-  static_assert(std::is_same<TS, TO>::value, "half storage: the I/O tensors are of the storage type");
-  static constexpr auto blend2 = blend2_bn_h_kernel<TS>;
-  static constexpr auto blend2_bwd = blend2_bn_bwd_h_kernel<TS>;
-  static constexpr auto pair_sums = pair_sums_h_kernel<TS>;
-  static constexpr auto blend1_da = blend1_da_h_kernel<TS>;
-  static constexpr auto gx = stage_gx_h_kernel<TS>;
-};
-// ... and float32 storage with float32 or half I/O (dhd_sfa_weights.io_dtype)
-template <class TO>
-struct Ew<float, TO> {
-  static constexpr auto blend2 = blend2_bn_kernel<TO>;
-  static constexpr auto blend2_bwd = blend2_bn_bwd_kernel<TO>;
-  static constexpr auto pair_sums = pair_sums_kernel;
-  static constexpr auto blend1_da = blend1_da_kernel;
-  static constexpr auto gx = stage_gx_kernel<TO>;
-};
 
 // Forward in up to three phases, cut at the two BatchNorm statistics points.  sync == nullptr: all phases in one call with
 // this call's own statistics.  sync != nullptr (nn.SyncBatchNorm): phases [lo, hi]; a phase that ends at a statistics point
@@ -1609,8 +1703,7 @@ int stage_forward(const Plan& p, const TS* x, const dhd_sfa_weights* w, TO* out,
   }
   if (hi <= 1) return DHD_OK;
   coef(bn2, y2, TF(T.tab_g2));   // bn2 has no consumer GEMM in the forward: the table slot is a sink
-  using E = Ew<TS, TO>;
-  hipLaunchKernelGGL(E::blend2, planes, dim3(kEwBlock), 0, st, x, SF(S.a1), y2, SF(S.scsh2), out, c, hw);
+  hipLaunchKernelGGL((blend2_bn_kernel<TS, TO>), planes, dim3(kEwBlock), 0, st, x, SF(S.a1), y2, SF(S.scsh2), out, c, hw);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -1620,7 +1713,6 @@ int stage_forward(const Plan& p, const TS* x, const dhd_sfa_weights* w, TO* out,
 template <class TS, class TO>
 int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const void* saved, const TO* gout, TO* gx,
                    const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw, int lo, int hi, double* sync, hipStream_t st) {
-  using E = Ew<TS, TO>;
   const int r = w->hidden;
   const SavedLayout S = saved_layout(b, c, hw, r, p.storage);
   const ScratchLayout T = scratch_layout(b, c, hw, r, p.storage);
@@ -1657,7 +1749,7 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
 
   if (lo <= 0) {
     // g2 = dL/ds2, BatchNorm-2 sums, go-part of dL/da
-    hipLaunchKernelGGL(E::blend2_bwd, planes, dim3(kEwBlock), 0, st, x, SF(S.a1), y2, SF(S.scsh2), SF(S.mean2), gout, g2, TF(T.part),
+    hipLaunchKernelGGL((blend2_bn_bwd_kernel<TS, TO>), planes, dim3(kEwBlock), 0, st, x, SF(S.a1), y2, SF(S.scsh2), SF(S.mean2), gout, g2, TF(T.part),
                        TF(T.da1), c, hw, tail2);
     if (sync) coef_out(tail2);
     DHD_LAUNCH_CHECK();
@@ -1673,7 +1765,7 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
     rc = launch_gemm(p, GemmCall<TS>{kDgrad2, g2, y2, cs, c, TF(T.tab_g2), sv + S.wp2t, nullptr, mask, nullptr, g1, y1, SF(S.scsh1)},
                      b, c, hw, st);
     if (rc != DHD_OK) return rc;
-    hipLaunchKernelGGL(E::pair_sums, planes, dim3(kEwBlock), 0, st, g1, y1, SF(S.mean1), TF(T.part), c, hw, tail1);
+    hipLaunchKernelGGL(pair_sums_kernel<TS>, planes, dim3(kEwBlock), 0, st, g1, y1, SF(S.mean1), TF(T.part), c, hw, tail1);
     if (sync) coef_out(tail1);
     DHD_LAUNCH_CHECK();
   }
@@ -1686,14 +1778,14 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
   // du = W1^T dy1
   rc = launch_gemm(p, GemmCall<TS>{kDgrad1, g1, y1, cs, c, TF(T.tab_g1), sv + S.wp1t, nullptr, nullptr, nullptr, du}, b, c, hw, st);
   if (rc != DHD_OK) return rc;
-  hipLaunchKernelGGL(E::blend1_da, planes, dim3(kEwBlock), 0, st, x, du, TF(T.da2), c, hw);
+  hipLaunchKernelGGL(blend1_da_kernel<TS>, planes, dim3(kEwBlock), 0, st, x, du, TF(T.da2), c, hw);
   hipLaunchKernelGGL(fc_backward_kernel, dim3(b), dim3(kEwBlock), (size_t)(c + r + kEwBlock) * sizeof(float), st, TF(T.da1), TF(T.da2),
                      SF(S.a1), SF(S.h), w->fc1_w, w->fc2_w, TF(T.dpre2), TF(T.dh), TF(T.ds), c, r);
   const int n_fc = r * 2 * c + c * r + r + c;
   const FcGradJob fcj = {TF(T.dpre2), TF(T.dh), SF(S.h), SF(S.s), grads->fc1_w, grads->fc1_b, grads->fc2_w, grads->fc2_b, b, r};
   const int fc_rows = dhd_cdiv(dhd_cdiv(n_fc, kEwBlock), kPlaneChunks);
   const dim3 planes_fc(kPlaneChunks, b * c + fc_rows);
-  hipLaunchKernelGGL(E::gx, planes_fc, dim3(kEwBlock), 0, st, SF(S.a1), y2, SF(S.scsh2), gout, du, TF(T.ds), gx, c, hw, fc_rows, fcj);
+  hipLaunchKernelGGL((stage_gx_kernel<TS, TO>), planes_fc, dim3(kEwBlock), 0, st, SF(S.a1), y2, SF(S.scsh2), gout, du, TF(T.ds), gx, c, hw, fc_rows, fcj);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -1703,7 +1795,7 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
 //   TWO_PASS  Gemm::cu / Gemm::cuh: mean + weight pack, fc, both BatchNorm tables, conv1 -> y1, conv2 + blend epilogue -> out
 //   ONE_PASS  Gemm::cuh: mean + weight pack, fc, both BatchNorm tables, sfa_onepass_h_kernel (sfa_half.h) -> out; no y1
 // Every form returns the bytes of stage_forward(training = 0): same kernels up to y1, and the blend epilogue applies
-// blend2_bn(_h)_kernel's expression to the value the unfused conv2 would have stored.
+// blend2_bn_kernel's expression (sfa_math.h: blend_gate, blend_out) to the value the unfused conv2 would have stored.
 inline bool infer_form_exists(const Plan& p, int form) {
   switch (form) {
     case DHD_SFA_INFER_AUTO: case DHD_SFA_INFER_UNFUSED: return true;

@@ -12,12 +12,15 @@
 //   batchnorm.hip                             __half / __hip_bfloat16     non-temporal       integer formula
 //   window.hip                                __half / __hip_bfloat16     plain              integer formula
 //   upsample.hip                              __half / __hip_bfloat16     plain              integer formula
-//   sfa_half.h, sfa_stage_half.h (storage)    _Float16 / __bf16           non-temporal       hardware convert
-//   sfa_stage.hip ld4 / st4 (edge tensors)    _Float16 / __bf16           non-temporal, 8 B  hardware convert
+//   sfa_half.h (storage)                      _Float16 / __bf16           non-temporal       hardware convert
+//   sfa_stage.hip element-wise (storage)      float / _Float16 / __bf16   per tensor (its    hardware convert
+//                                                                         policy block)
+//   sfa_stage.hip IoVec (edge tensors)        float / _Float16 / __bf16   non-temporal, 16 B hardware convert
+//                                                                         or 8 B (half I/O on float32 storage)
 //   mghs_pool.hip (dense views)               _Float16 / __bf16           non-temporal       hardware convert
 //   deform.hip, mghs_softmax.hip (scalars)    _Float16 / __bf16           plain, per element hardware convert ((T)v)
 //
-// sfa_stage.hip's st4 and mghs_pool.hip's pack_vox convert element by element ((T)v, the same hardware convert) instead of through
+// sfa_stage.hip's 8-byte IoVec store and mghs_pool.hip's pack_vox convert element by element ((T)v, the same hardware convert) instead of through
 // Pair<T>::narrow: the pairwise form compiles to the same instructions in another order, and their kernels keep the order they have.
 //
 // Host side: with_dtype maps a DHD_F32 / DHD_F16 / DHD_BF16 code of the C ABI to an element type of either spelling.
@@ -111,16 +114,22 @@ template <class T> __device__ __forceinline__ raw16<T> narrow16(const float* v) 
 // 16-byte loads and stores of T (p 16-byte aligned), non-temporal (NT) or plain
 template <class T, bool NT> struct Vec16 {
   static constexpr int N = kVec16<T>;
-  static __device__ __forceinline__ void load(const T* p, float* v) {
-    const raw16<T>* q = reinterpret_cast<const raw16<T>*>(p);
-    if constexpr (NT) widen16<T>(__builtin_nontemporal_load(q), v);
-    else widen16<T>(*q, v);
+  // vector i of p, the 16 bytes as they are (widen16 them where they are used) ...
+  static __device__ __forceinline__ raw16<T> ld(const T* p, size_t i = 0) {
+    const raw16<T>* q = reinterpret_cast<const raw16<T>*>(p) + i;
+    if constexpr (NT) return __builtin_nontemporal_load(q);
+    else return *q;
   }
-  static __device__ __forceinline__ void store(T* p, const float* v) {
-    raw16<T>* q = reinterpret_cast<raw16<T>*>(p);
-    if constexpr (NT) __builtin_nontemporal_store(narrow16<T>(v), q);
-    else *q = narrow16<T>(v);
+  static __device__ __forceinline__ void st(T* p, size_t i, raw16<T> w) {
+    raw16<T>* q = reinterpret_cast<raw16<T>*>(p) + i;
+    if constexpr (NT) __builtin_nontemporal_store(w, q);
+    else *q = w;
   }
+  // ... and as kVec16<T> floats
+  static __device__ __forceinline__ void load(const T* p, size_t i, float* v) { widen16<T>(ld(p, i), v); }
+  static __device__ __forceinline__ void load(const T* p, float* v) { load(p, 0, v); }
+  static __device__ __forceinline__ void store(T* p, size_t i, const float* v) { st(p, i, narrow16<T>(v)); }
+  static __device__ __forceinline__ void store(T* p, const float* v) { store(p, 0, v); }
 };
 
 // Host: the element type of a dtype code of the C ABI, in HIP's spelling (these appear in the mangled names of the batchnorm,

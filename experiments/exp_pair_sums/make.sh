@@ -1,6 +1,6 @@
 #!/bin/bash
 # VERDICT r5 item 3, priced by measurement instead of arithmetic: what does the data-gradient GEMM of the half-storage stage
-# (pw_gemm_cuh_kernel, EPI = 1) cost when its epilogue also does pair_sums_h's work -- load the y1 tile of the rows it is about to store
+# (pw_gemm_cuh_kernel, EPI = 1) cost when its epilogue also does the work of pair_sums_kernel<TS> (then pair_sums_h_kernel) -- load the y1 tile of the rows it is about to store
 # and accumulate S1 = sum g1, S2 = sum g1 (y1 - mean) per channel (one row of partial sums per workgroup)?
 # The product sources are NOT edited: this script copies dhd_amd/csrc into experiments/build/exp_pair_sums/, patches the copy of sfa_half.h
 # (patch.py) and builds experiments/gemm_cuh_bench.hip against the copy, once plain (A) and once with -DDHD_EXP_PAIR (B).

@@ -1,5 +1,6 @@
 """Patches the COPY of sfa_half.h / gemm_cuh_bench.hip made by make.sh (the product sources stay untouched): with -DDHD_EXP_PAIR the
-data-gradient GEMM (EPI = 1) also loads the y tile of the rows it stores and accumulates pair_sums_h's two sums per channel."""
+data-gradient GEMM (EPI = 1) also loads the y tile of the rows it stores and accumulates the two sums of pair_sums_kernel<TS> (sfa_stage.hip; pair_sums_h_kernel when this was measured) per channel.
+The strings below are exact lines of sfa_half.h: a change there has to be followed here."""
 import sys
 d = sys.argv[1]
 p = d + '/dhd_amd/csrc/sfa_half.h'
@@ -18,9 +19,9 @@ __device__ float* g_exp_stat = nullptr;         // [grid][2][C]
 __global__ void exp_set_kernel(const void* y, const float* m, float* st_) { g_exp_y = y; g_exp_mean = m; g_exp_stat = st_; }
 #endif
 // y[b, co, p] = TS( sum_ci TS(W[co, ci]) * TS(act(c0[b,ci]*in0[b,ci,p] + c1[b,ci]*in1[b,ci,p] + c2[b,ci])) (+ epilogue) )""")
-rep("""  if (EPI == 0)
+rep("""  if (EPI == 0 || EPI == 3)
     for (int i = tid; i < C; i += WAVES * 64) bias_lds[i] = bias[i];
-""", """  if (EPI == 0)
+""", """  if (EPI == 0 || EPI == 3)
     for (int i = tid; i < C; i += WAVES * 64) bias_lds[i] = bias[i];
 #ifdef DHD_EXP_PAIR
   if (EPI == 1)
@@ -41,15 +42,15 @@ rep("""    // ---- MFMA phase: D[channel][pixel] over all K, two 32-pixel halves
     // ---- MFMA phase: D[channel][pixel] over all K, two 32-pixel halves -------------------------------------------------
 """)
 rep("""        } else {
-          pk = narrow8<TS>(o);
+          pk = narrow16<TS>(o);
         }
 """, """        } else {
-          pk = narrow8<TS>(o);
+          pk = narrow16<TS>(o);
 #ifdef DHD_EXP_PAIR
           if (EPI == 1) {
             float r[8], yy[8];
-            widen8<TS>(pk, r);
-            widen8<TS>(yv[k], yy);
+            widen16<TS>(pk, r);
+            widen16<TS>(yv[k], yy);
             const float mu = bias_lds[kbase + g + 8 * k];
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -72,7 +73,7 @@ open(p, 'w').write(s)
 p = d + '/experiments/gemm_cuh_bench.hip'
 s = open(p).read()
 rep('#include "../dhd_amd/csrc/sfa_stage.hip"', '#include "../dhd_amd/csrc/sfa_stage.hip"')
-rep("""  if (launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wp, bias, nullptr, stat, y, 0, B, C, HW, st, &rows)) printf("launch failed\\n");
+rep("""  if (launch_gemm_cu<TS>({kConv1, x, x + plane, 2 * plane, C, coef, wp, bias, nullptr, stat, y}, B, C, HW, st, &rows)) printf("launch failed\\n");
 """, """#ifdef DHD_EXP_PAIR
   {
     const void* yp = g; const float* mp = coef; float* sp = stat;
@@ -81,7 +82,7 @@ rep("""  if (launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wp,
     printf("  [DHD_EXP_PAIR: dgrad2's epilogue also loads the y tile and accumulates pair_sums' two sums]\\n");
   }
 #endif
-  if (launch_pw_gemm_cuh<TS>(x, x + plane, 2 * plane, C, coef, false, wp, bias, nullptr, stat, y, 0, B, C, HW, st, &rows)) printf("launch failed\\n");
+  if (launch_gemm_cu<TS>({kConv1, x, x + plane, 2 * plane, C, coef, wp, bias, nullptr, stat, y}, B, C, HW, st, &rows)) printf("launch failed\\n");
 """)
 open(p, 'w').write(s)
 print('patched')

@@ -28,7 +28,8 @@ rm -rf $OUT/hp $OUT/mo $OUT/pf $OUT/pw
 fi
 cd /tmp
 if [[ " $WHAT " == *" hotpath "* ]]; then
-# round 5: the half-storage SFA stage alone (its kernels have their own names: no clash with the float32 hot path)
+# round 5: the half-storage SFA stage alone (a run of its own: its element-wise kernels are the float32 stage's templates at
+# another storage type, `blend2_bn_kernel<_Float16, _Float16>` ..., and up to r8 were `*_h_kernel`)
 H="python $R/experiments/sfa_half.py 4 6 fp16 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/hs -o hs -- python $R/experiments/sfa_half.py 4 20 fp16 1 > $OUT/sfa_half_fp16.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/hb -o hb -- python $R/experiments/sfa_half.py 4 20 bf16 1 > $OUT/sfa_half_bf16.log 2>&1
@@ -37,7 +38,7 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/hw -o hw -
 cp $(find $OUT/hs -name 'hs_kernel_stats.csv') $OUT/sfa_half_fp16_kernel_stats.csv
 cp $(find $OUT/hb -name 'hb_kernel_stats.csv') $OUT/sfa_half_bf16_kernel_stats.csv
 head -1 $(find $OUT/hf -name 'hf_counter_collection.csv') > $OUT/pmc_sfa_half.csv
-grep -h "_h_kernel\|cuh_kernel\|wgrad_h\|wgrad_reduce\|fc_forward\|fc_backward\|bn_stats_finalize" $(find $OUT/hf -name 'hf_counter_collection.csv') $(find $OUT/hw -name 'hw_counter_collection.csv') >> $OUT/pmc_sfa_half.csv
+grep -h "_h_kernel\|plane_mean\|blend[12]_\|pair_sums\|stage_gx\|cuh_kernel\|wgrad_h\|wgrad_reduce\|fc_forward\|fc_backward\|bn_stats_finalize" $(find $OUT/hf -name 'hf_counter_collection.csv') $(find $OUT/hw -name 'hw_counter_collection.csv') >> $OUT/pmc_sfa_half.csv
 rm -rf $OUT/hs $OUT/hb $OUT/hf $OUT/hw
 fi
 cd /tmp
