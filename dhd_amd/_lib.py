@@ -224,6 +224,15 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def dense16(t, memory_format=torch.contiguous_format):
+    """`t` as the kernels that move 16-byte vectors read a tensor: dense in `memory_format` at a 16-byte aligned address.  `t`
+    itself where it already is that (every freshly allocated tensor), else a copy -- of a strided, expanded or sliced view by
+    `.contiguous`, of a dense view at an odd storage offset by `.clone` (torch's strided copy both times).  The library refuses
+    misaligned pointers (DHD_EINVAL), so a wrapper that forgets this raises instead of computing on the wrong bytes."""
+    t = t.contiguous(memory_format=memory_format)
+    return t.clone(memory_format=torch.preserve_format) if t.data_ptr() % 16 else t
+
+
 def require_gpu_tensor(t, dtype, name):
     if not t.is_cuda:
         raise DhdError(f'{name} must live on the GPU: dhd_amd runs only as HIP kernels (got {t.device})')

@@ -39,9 +39,9 @@ class _BNTrain(torch.autograd.Function):
         hw = x[0, 0].numel()
         lib = _lib.load()
         dev = x.device
-        gy = gy.contiguous()
         if gy.dtype != x.dtype:
             gy = gy.to(x.dtype)
+        gy = _lib.dense16(gy)                      # the gradient may be any view: the kernels move 16-byte vectors
         with torch.cuda.device(dev):
             gx = torch.empty_like(x)
             dgamma = torch.empty(c, dtype=torch.float32, device=dev)
@@ -93,9 +93,9 @@ class _BNTrainNHWC(torch.autograd.Function):
         rows = n * h * w
         lib = _lib.load()
         dev = x.device
-        gy = gy.contiguous(memory_format=torch.channels_last)
         if gy.dtype != x.dtype:
             gy = gy.to(x.dtype)
+        gy = _lib.dense16(gy, torch.channels_last)
         want_res = bool(ctx.flags & BN_ADD) and ctx.needs_input_grad[8]
         with torch.cuda.device(dev):
             gx = torch.empty_like(x)

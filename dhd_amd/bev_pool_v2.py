@@ -20,6 +20,13 @@ def _as(t, dtype):
     return t if (t.dtype == dtype and t.is_contiguous()) else t.contiguous().to(dtype)
 
 
+def _as16(t, dtype):
+    """`_as` for the tensors the fused entry points read as 16-byte vectors (feat, out_grad: the library refuses a misaligned
+    pointer): a dense view at an odd storage offset is copied.  The three-step entry points pick their scalar kernels instead."""
+    t = _as(t, dtype)
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 class _on:
     """`with torch.cuda.device(dev)` only when `dev` is not the current device (the context manager costs ~10 us per use)."""
 
@@ -142,7 +149,7 @@ class _FusedPool(torch.autograd.Function):
         i32, f32 = torch.int32, torch.float32
         ranks_bev = _as(ranks_bev, i32)
         depth = _as(depth, f32)
-        feat = _as(feat, f32)
+        feat = _as16(feat, f32)
         ranks_depth = _as(ranks_depth, i32)
         ranks_feat = _as(ranks_feat, i32)
         interval_lengths = _as(interval_lengths, i32)
@@ -182,7 +189,7 @@ class _FusedPool(torch.autograd.Function):
         b, dz, dy, dx, c, n_iv, sizes = ctx.dims
         rd, rf, rb, starts, lengths = _regrouped(lib, ranks_depth, ranks_feat, ranks_bev, feat.numel() // c)
         dev = depth.device
-        out_grad = _as(out_grad, torch.float32)
+        out_grad = _as16(out_grad, torch.float32)
         with _on(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             # one zero-fill for both gradients (bev_pool.py:67-68); feat's part starts on a 16-byte boundary

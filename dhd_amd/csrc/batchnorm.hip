@@ -526,6 +526,7 @@ int dhd_bn_train_forward(const void* x, int dtype, int n, int c, int hw, const f
                          float* running_var, float factor, float eps, void* y, float* save_mean, float* save_rstd, void* workspace,
                          void* stream) {
   if (!x || !y || !save_mean || !save_rstd || !workspace) return DHD_EINVAL;
+  if (!dhd_aligned(16, x, y)) return DHD_EINVAL;   // Vec16 accesses
   if (!dhd_bn_supported(dtype, n, c, hw)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);
@@ -538,6 +539,7 @@ int dhd_bn_train_forward(const void* x, int dtype, int n, int c, int hw, const f
 int dhd_bn_train_backward(const void* x, const void* grad_y, int dtype, int n, int c, int hw, const float* gamma, const float* save_mean,
                           const float* save_rstd, void* grad_x, float* dgamma, float* dbeta, void* workspace, void* stream) {
   if (!x || !grad_y || !grad_x || !save_mean || !save_rstd || !workspace) return DHD_EINVAL;
+  if (!dhd_aligned(16, x, grad_y, grad_x)) return DHD_EINVAL;
   if (!dhd_bn_supported(dtype, n, c, hw)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);
@@ -559,6 +561,7 @@ int dhd_bn_nhwc_train_forward(const void* x, const void* residual, int dtype, lo
                               float* save_mean, float* save_rstd, float* save_affine, void* workspace, void* stream) {
   if (!x || !y || !save_mean || !save_rstd || !save_affine || !workspace) return DHD_EINVAL;
   if ((flags & DHD_BN_ADD) && !residual) return DHD_EINVAL;
+  if (!dhd_aligned(16, x, y, residual)) return DHD_EINVAL;
   if (!bn_cl_shape_ok(dtype, rows, c)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);
@@ -575,6 +578,7 @@ int dhd_bn_nhwc_train_backward(const void* x, const void* y, const void* grad_y,
   if (!x || !grad_y || !grad_x || !save_mean || !save_rstd || !workspace) return DHD_EINVAL;
   if ((flags & DHD_BN_ADD) && !y) return DHD_EINVAL;
   if ((flags & DHD_BN_RELU) && !(flags & DHD_BN_ADD) && !save_affine) return DHD_EINVAL;
+  if (!dhd_aligned(16, x, y, grad_y, grad_x, grad_residual)) return DHD_EINVAL;
   if (!bn_cl_shape_ok(dtype, rows, c)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   float* ws = static_cast<float*>(workspace);

@@ -24,6 +24,13 @@ static inline hipStream_t dhd_stream(void* s) { return reinterpret_cast<hipStrea
 
 static inline int dhd_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Every pointer given is a multiple of `bytes` (a power of two); a null pointer counts as aligned.  The host-side test of the
+// entry points whose kernels access a caller's tensor in 16-byte vectors (vec16.h): a misaligned view is refused before any launch.
+template <class... P>
+static inline bool dhd_aligned(unsigned bytes, P... p) {
+  return ((... | reinterpret_cast<uintptr_t>(p)) & (uintptr_t)(bytes - 1)) == 0;
+}
+
 // Sum over the `width` (power of two, <= 64) lanes that share lane_id / width.
 __device__ __forceinline__ float group_sum(float v, int width) {
   for (int m = width >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, DHD_WAVE);

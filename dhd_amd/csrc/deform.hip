@@ -624,6 +624,8 @@ __global__ __launch_bounds__(kBlock) void stereo_cost_volume_pair_kernel(const f
 extern "C" int dhd_stereo_cost_volume(const float* prev_nhwc, const float* curr_nhwc, const float* grid, int bn, int c, int h, int w,
                                       int n_depth, float bias, int flag_channel, float* out, void* stream) {
   if (!prev_nhwc || !curr_nhwc || !grid || !out || bn <= 0 || c <= 0 || h <= 0 || w <= 0 || n_depth <= 0) return DHD_EINVAL;
+  // a pixel's channels are read in 16-byte groups, a sampling position as one float2
+  if (!dhd_aligned(16, prev_nhwc, curr_nhwc) || !dhd_aligned(8, grid)) return DHD_EINVAL;
   if ((c & 3) != 0 || c > 1024 || n_depth > kCvMaxD || flag_channel < 0 || flag_channel >= c) return DHD_EUNSUPPORTED;
   const long n_pix = (long)bn * h * w;
   if (n_pix >= (1L << 31) / n_depth) return DHD_EUNSUPPORTED;

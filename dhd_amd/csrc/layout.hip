@@ -67,6 +67,8 @@ extern "C" {
 
 int dhd_transpose_batched(const void* in, void* out, int elem_bytes, long batch, int rows, int cols, void* stream) {
   if (!in || !out) return DHD_EINVAL;
+  // element accesses, except the pair kernel's 4-byte words of two 2-byte elements
+  if (!dhd_aligned(elem_bytes == 2 && ((rows | cols) & 1) ? 2 : 4, in, out)) return DHD_EINVAL;
   if ((elem_bytes != 2 && elem_bytes != 4) || batch <= 0 || rows <= 0 || cols <= 0) return DHD_EUNSUPPORTED;
   const int tiles_r = dhd_cdiv(rows, kTile), tiles_c = dhd_cdiv(cols, kTile);
   const long blocks = batch * tiles_r * tiles_c;

@@ -229,6 +229,7 @@ inline int make_views(const Layout& L, T* const bases[DHD_MAX_GRIDS], const dhd_
       if (o->dtype != DHD_F32 && (L.grid[g].n[0] & 1)) return DHD_EUNSUPPORTED;   // 4 rows of nx voxels in 8-voxel vectors
     } else {
       if (!bases || !bases[g]) return DHD_EINVAL;
+      if (reinterpret_cast<uintptr_t>(bases[g]) & 15) return DHD_EINVAL;   // rows move as 16-byte vectors on either path, as with views
       o->p[g] = bases[g];
       o->sb[g] = (long)L.grid[g].n[2] * L.C * plane; o->sz[g] = (long)L.C * plane; o->sc[g] = plane;
     }

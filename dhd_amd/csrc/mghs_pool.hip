@@ -893,6 +893,7 @@ int dhd_mghs_forward_gather(const dhd_mghs_desc* desc, const float* depth, const
   int rc = make_layout(desc, workspace, &L);
   if (rc) return rc;
   if (!workspace || !depth || !feat_nhwc) return DHD_EINVAL;
+  if (L.compact && !dhd_aligned(16, feat_nhwc)) return DHD_EINVAL;   // a 64-channel row is read as 16-byte vectors
   if (!L.compact) return DHD_OK;  // the generic path gathers inside its row kernel
   hipStream_t st = dhd_stream(stream);
   // column form for the full-height grid (Layout::columns), sorted gather for the rest
@@ -929,6 +930,7 @@ static int forward_stream_impl(const dhd_mghs_desc* desc, const float* depth, co
   int rc = make_layout(desc, workspace, &L);
   if (rc) return rc;
   if (!workspace || !depth || !feat_nhwc || (!out && !views)) return DHD_EINVAL;
+  if (L.compact && !dhd_aligned(16, feat_nhwc)) return DHD_EINVAL;
   OutPtrs o;
   if ((rc = make_views<OutPtrs, float>(L, out, views, &o))) return rc;
   hipStream_t st = dhd_stream(stream);
@@ -978,6 +980,7 @@ static int backward_impl(const dhd_mghs_desc* desc, const float* depth, const fl
   int rc = make_layout(desc, workspace, &L);
   if (rc) return rc;
   if (!workspace || !depth || !feat_nhwc || (!out_grad && !views) || !depth_grad || !feat_grad_nhwc) return DHD_EINVAL;
+  if (L.compact && !dhd_aligned(16, feat_nhwc, feat_grad_nhwc)) return DHD_EINVAL;   // mghs_pixel_bwd: 16-byte rows
   InPtrs in;
   if ((rc = make_views<InPtrs, const float>(L, out_grad, views, &in))) return rc;
   hipStream_t st = dhd_stream(stream);

@@ -225,9 +225,10 @@ inline bool bad(int b, int c, int hw) { return b <= 0 || c <= 0 || hw <= 0; }
 
 }  // namespace
 
-#define DHD_SFA_LAUNCH(kernel, grid, stream, ...)                                                   \
+// VEC (float4 accesses) needs planes of a multiple of 4 floats AND 16-byte aligned tensors; anything else takes the scalar kernels
+#define DHD_SFA_LAUNCH(vec, kernel, grid, stream, ...)                                              \
   do {                                                                                              \
-    if ((hw & 3) == 0)                                                                              \
+    if (vec)                                                                                        \
       hipLaunchKernelGGL(kernel<true>, grid, dim3(kBlock), 0, dhd_stream(stream), __VA_ARGS__);     \
     else                                                                                            \
       hipLaunchKernelGGL(kernel<false>, grid, dim3(kBlock), 0, dhd_stream(stream), __VA_ARGS__);    \
@@ -238,19 +239,19 @@ extern "C" {
 
 int dhd_sfa_channel_mean(const float* x, float* s, int b, int c2, int hw, void* stream) {
   if (!x || !s || bad(b, c2, hw)) return DHD_EINVAL;
-  DHD_SFA_LAUNCH(channel_mean_kernel, dim3(b * c2), stream, x, s, hw);
+  DHD_SFA_LAUNCH((hw & 3) == 0 && dhd_aligned(16, x), channel_mean_kernel, dim3(b * c2), stream, x, s, hw);
   return DHD_OK;
 }
 
 int dhd_sfa_blend1(const float* x, const float* a1, float* u, int b, int c, int hw, void* stream) {
   if (!x || !a1 || !u || bad(b, c, hw)) return DHD_EINVAL;
-  DHD_SFA_LAUNCH(blend1_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, u, c, hw);
+  DHD_SFA_LAUNCH((hw & 3) == 0 && dhd_aligned(16, x, u), blend1_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, u, c, hw);
   return DHD_OK;
 }
 
 int dhd_sfa_blend2(const float* x, const float* a1, const float* s2, float* out, int b, int c, int hw, void* stream) {
   if (!x || !a1 || !s2 || !out || bad(b, c, hw)) return DHD_EINVAL;
-  DHD_SFA_LAUNCH(blend2_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, s2, out, c, hw);
+  DHD_SFA_LAUNCH((hw & 3) == 0 && dhd_aligned(16, x, s2, out), blend2_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, s2, out, c, hw);
   return DHD_OK;
 }
 
@@ -258,20 +259,20 @@ int dhd_sfa_blend2_backward(const float* x, const float* a1, const float* s2, co
                             float* ga1, int b, int c, int hw, void* stream) {
   if (!x || !a1 || !s2 || !go || !gx || !gs2 || !ga1 || bad(b, c, hw)) return DHD_EINVAL;
   DHD_HIP(hipMemsetAsync(ga1, 0, (size_t)b * c * 4, dhd_stream(stream)));
-  DHD_SFA_LAUNCH(blend2_bwd_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, s2, go, gx, gs2, ga1, c, hw);
+  DHD_SFA_LAUNCH((hw & 3) == 0 && dhd_aligned(16, x, s2, go, gx, gs2), blend2_bwd_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, s2, go, gx, gs2, ga1, c, hw);
   return DHD_OK;
 }
 
 int dhd_sfa_blend1_backward(const float* x, const float* a1, const float* gu, float* gx, float* ga1, int b, int c, int hw,
                             void* stream) {
   if (!x || !a1 || !gu || !gx || !ga1 || bad(b, c, hw)) return DHD_EINVAL;
-  DHD_SFA_LAUNCH(blend1_bwd_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, gu, gx, ga1, c, hw);
+  DHD_SFA_LAUNCH((hw & 3) == 0 && dhd_aligned(16, x, gu, gx), blend1_bwd_kernel, dim3(kChunksPerPlane, b * c), stream, x, a1, gu, gx, ga1, c, hw);
   return DHD_OK;
 }
 
 int dhd_sfa_mean_backward(const float* gs, float* gx, int b, int c2, int hw, void* stream) {
   if (!gs || !gx || bad(b, c2, hw)) return DHD_EINVAL;
-  DHD_SFA_LAUNCH(mean_bwd_kernel, dim3(kChunksPerPlane, b * c2), stream, gs, gx, hw);
+  DHD_SFA_LAUNCH((hw & 3) == 0 && dhd_aligned(16, gx), mean_bwd_kernel, dim3(kChunksPerPlane, b * c2), stream, gs, gx, hw);
   return DHD_OK;
 }
 

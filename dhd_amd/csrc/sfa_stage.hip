@@ -1917,6 +1917,7 @@ int with_types(const Plan& p, int io_dtype, F&& f) {
 static int stage_forward_entry(const void* x, const dhd_sfa_weights* w, void* out, void* saved, void* scratch, int b, int c, int hw,
                                int lo, int hi, double* sync, void* stream) {
   if (!x || !w || !saved || !scratch || b <= 0 || (hi == 2 && !out)) return DHD_EINVAL;
+  if (!dhd_aligned(16, x, out, saved, scratch)) return DHD_EINVAL;   // 16-byte vector accesses in every kernel of the stage
   if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
   if (!w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b || !w->conv1_w || !w->conv1_b || !w->bn1_w || !w->bn1_b || !w->conv2_w ||
       !w->conv2_b || !w->bn2_w || !w->bn2_b)
@@ -1936,6 +1937,7 @@ static int stage_backward_entry(const void* x, const dhd_sfa_weights* w, const v
                                 const dhd_sfa_grads* grads, void* scratch, int b, int c, int hw, int lo, int hi, double* sync,
                                 void* stream) {
   if (!x || !w || !saved || !gout || !grads || !scratch || b <= 0 || (hi == 2 && !gx)) return DHD_EINVAL;
+  if (!dhd_aligned(16, x, saved, gout, gx, scratch)) return DHD_EINVAL;
   if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
   if (!grads->fc1_w || !grads->fc1_b || !grads->fc2_w || !grads->fc2_b || !grads->conv1_w || !grads->conv1_b || !grads->bn1_w ||
       !grads->bn1_b || !grads->conv2_w || !grads->conv2_b || !grads->bn2_w || !grads->bn2_b)
@@ -1953,6 +1955,7 @@ static int stage_backward_entry(const void* x, const dhd_sfa_weights* w, const v
 static int stage_infer_entry(const void* x, const dhd_sfa_weights* w, void* out, void* scratch, int b, int c, int hw, int form,
                              void* stream) {
   if (!x || !w || !out || !scratch || b <= 0 || form < DHD_SFA_INFER_AUTO || form > DHD_SFA_INFER_ONE_PASS) return DHD_EINVAL;
+  if (!dhd_aligned(16, x, out, scratch)) return DHD_EINVAL;
   if (!stage_supported(c, hw) || w->hidden <= 0) return DHD_EUNSUPPORTED;
   if (!w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b || !w->conv1_w || !w->conv1_b || !w->bn1_w || !w->bn1_b || !w->conv2_w ||
       !w->conv2_b || !w->bn2_w || !w->bn2_b)

@@ -194,6 +194,8 @@ int up_run(bool bwd, const T* in, T* out, int layout, const Geom& g, hipStream_t
 
 int up_dispatch(bool bwd, const void* in, void* out, int dtype, int layout, int n, int c, int hin, int win, int hout, int wout, void* stream) {
   if (!in || !out) return DHD_EINVAL;
+  // channels_last rows move as 16-byte vectors; the NCHW kernels access single elements
+  if (!dhd_aligned(layout == 1 ? 16 : (dtype == DHD_F32 ? 4 : 2), in, out)) return DHD_EINVAL;
   if (!up_ok(dtype, layout, n, c, hin, win, hout, wout)) return DHD_EUNSUPPORTED;
   const Geom g = make_geom(n, c, hin, win, hout, wout);
   hipStream_t st = dhd_stream(stream);

@@ -83,6 +83,7 @@ int window_launch(const void* in, void* out, const WinGeom& g, int reverse, hipS
 extern "C" int dhd_window_rows(const void* in, void* out, int in_dtype, int out_dtype, int b, int h, int w, int c, int window, int shift,
                                int reverse, void* stream) {
   if (!in || !out) return DHD_EINVAL;
+  if (!dhd_aligned(16, in, out)) return DHD_EINVAL;   // load8 / store8
   if (in_dtype < 0 || in_dtype > 2 || out_dtype < 0 || out_dtype > 2 || b <= 0 || h <= 0 || w <= 0 || c <= 0 || (c & 7) || window <= 0 ||
       shift < 0 || shift >= window)
     return DHD_EUNSUPPORTED;

@@ -362,6 +362,8 @@ class _LiftNetBase(nn.Module):
         prev_l = mghs_op._nchw_to_nhwc(prev.float().contiguous())
         curr_l = mghs_op._nchw_to_nhwc(curr.float().contiguous())
         grid = grid.float().contiguous()
+        if grid.data_ptr() % 8:     # a sampling position is read as one float2
+            grid = grid.clone()
         with torch.cuda.device(dev):
             out = torch.empty((bn, n_depth, h, w), dtype=torch.float32, device=dev)
             _lib.check(_lib.load().dhd_stereo_cost_volume(_lib.ptr(prev_l), _lib.ptr(curr_l), _lib.ptr(grid), bn, c, h, w, n_depth,

@@ -241,8 +241,7 @@ class _UpsampleBilinear(torch.autograd.Function):
     def forward(ctx, x, size):
         from . import _lib
         geom = _UpsampleBilinear._geom(x, size)
-        if not geom[1]:
-            x = x.contiguous()
+        x = _lib.dense16(x, torch.channels_last if geom[1] else torch.contiguous_format)
         lib = _lib.load()
         with torch.cuda.device(x.device):
             y = torch.empty((geom[2], geom[3], geom[6], geom[7]), dtype=x.dtype, device=x.device,
@@ -255,7 +254,7 @@ class _UpsampleBilinear(torch.autograd.Function):
     def backward(ctx, gy):
         from . import _lib
         geom = ctx.geom
-        gy = gy.contiguous(memory_format=torch.channels_last if geom[1] else torch.contiguous_format)
+        gy = _lib.dense16(gy, torch.channels_last if geom[1] else torch.contiguous_format)   # any view of a gradient
         lib = _lib.load()
         with torch.cuda.device(gy.device):
             gx = torch.empty((geom[2], geom[3], geom[4], geom[5]), dtype=gy.dtype, device=gy.device,
@@ -285,7 +284,9 @@ class Upsample(nn.Upsample):
             sf = self.scale_factor if isinstance(self.scale_factor, (tuple, list)) else (self.scale_factor, self.scale_factor)
             size = (int(h * sf[0]), int(w * sf[1]))        # floor(in * scale), as F.interpolate
         geom = _UpsampleBilinear._geom(x, size)
-        if geom[0] < 0 or x.data_ptr() % 16 or not _lib.load().dhd_upsample_bilinear_supported(*geom):   # (16-byte vector loads)
+        # (a view that is strided or sits at an odd storage offset is copied by the node: torch's own half kernels add the
+        # gradient up in half precision, 6x the error of the gather here on a bfloat16 (2, 8, 18, 26) gradient)
+        if geom[0] < 0 or not _lib.load().dhd_upsample_bilinear_supported(*geom):
             if x.dtype in (torch.float16, torch.bfloat16) and torch.is_autocast_enabled():
                 with torch.autocast('cuda', enabled=False):
                     return super().forward(x)

@@ -104,11 +104,15 @@ class ModelEMA:
             dense = (v.is_contiguous() and m.is_contiguous()) or (
                 v.stride() == m.stride() and v.is_contiguous(memory_format=torch.channels_last)
                 and m.is_contiguous(memory_format=torch.channels_last)) if v.dim() == 4 else (v.is_contiguous() and m.is_contiguous())
-            if v.dtype != torch.float32 or m.dtype != torch.float32 or not dense:
-                raise _lib.DhdError('ModelEMA: GPU state must be dense float32 with one layout in the model and its EMA copy '
-                                    '(the reference keeps the EMA in FP32)')
+            if v.dtype != torch.float32 or m.dtype != torch.float32:
+                raise _lib.DhdError('ModelEMA: GPU state must be float32 in the model and its EMA copy (the reference keeps the EMA in FP32)')
             if v.device != m.device or v.shape != m.shape:
                 raise _lib.DhdError('ModelEMA: EMA and model state differ in device or shape')
+            if not dense:
+                # a strided view (a parameter sliced out of a wider buffer with a step, two different layouts): the reference's own
+                # expression through torch, which takes any strides -- the same two roundings as the kernel, the same bits
+                cpu.append((v, m))
+                continue
             by_dev.setdefault(v.device, []).append((v, m))
         if by_dev:
             _lib.load()  # GPU state without the library: fail here, not silently on another path

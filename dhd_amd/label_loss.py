@@ -44,6 +44,13 @@ class _BinBCE(torch.autograd.Function):
         pred = _lib.require_gpu_tensor(pred.contiguous(), torch.float32, 'prediction map')
         bn, c = pred.shape[:2]
         hw = pred[0, 0].numel()
+        # the kernels read the labels as dense int16 (bn * hw): any integer dtype and any view is converted, never reinterpreted
+        labels = []
+        for name, t in (('bin_idx', bin_idx), ('fg_bin', fg_bin)):
+            if t.dtype.is_floating_point or t.dtype == torch.bool or t.numel() != bn * hw:
+                raise _lib.DhdError(f'{name} must hold one integer bin index per pixel ({bn * hw}), got {t.dtype} x {t.numel()}')
+            labels.append(_lib.require_gpu_tensor(t.reshape(-1).to(torch.int16).contiguous(), torch.int16, name))
+        bin_idx, fg_bin = labels
         lib = _lib.load()
         dev = pred.device
         with torch.cuda.device(dev):

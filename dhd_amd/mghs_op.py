@@ -173,6 +173,7 @@ def height_band(height, height_range, mask_range):
 
 def _nchw_to_nhwc(x):
     lib = _lib.load()
+    x = _f32(x, 'feat (B*N, C, fH, fW)')      # raw layouts: a strided view is refused, never read as if dense
     bn, c, fh, fw = x.shape
     out = torch.empty((bn, fh, fw, c), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
@@ -183,6 +184,7 @@ def _nchw_to_nhwc(x):
 
 def _nhwc_to_nchw(x):
     lib = _lib.load()
+    x = _f32(x, 'feat (B*N, fH, fW, C)')
     bn, fh, fw, c = x.shape
     out = torch.empty((bn, c, fh, fw), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
@@ -325,8 +327,15 @@ def _ptr_array(tensors):
     return arr
 
 
+def _pool_inputs(depth, feat_nhwc):
+    """The raw-layout helpers below take dense float32 GPU tensors and refuse anything else (DhdError); the compact path's
+    16-byte alignment of feat_nhwc and of the pooled tensors is checked by the library."""
+    return _f32(depth, 'depth'), _f32(feat_nhwc, 'feat_nhwc')
+
+
 def pool_forward(plan, depth, feat_nhwc, workspace):
     lib = _lib.load()
+    depth, feat_nhwc = _pool_inputs(depth, feat_nhwc)
     dev = depth.device
     outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in plan.out_shapes()]
     arr = _ptr_array(outs)
@@ -341,6 +350,7 @@ def pool_forward_phases(plan, depth, feat_nhwc, workspace, between=None):
     """pool_forward as its two C-ABI phases; `between()` runs after the gather launch (bench.py
     records a HIP event there so that the streaming kernel is timed on its own)."""
     lib = _lib.load()
+    depth, feat_nhwc = _pool_inputs(depth, feat_nhwc)
     dev = depth.device
     outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in plan.out_shapes()]
     arr = _ptr_array(outs)
@@ -357,6 +367,8 @@ def pool_forward_phases(plan, depth, feat_nhwc, workspace, between=None):
 
 def pool_backward(plan, depth, feat_nhwc, out_grads, workspace):
     lib = _lib.load()
+    depth, feat_nhwc = _pool_inputs(depth, feat_nhwc)
+    out_grads = [_f32(g, 'out_grad') for g in out_grads]
     dev = depth.device
     depth_grad = torch.empty_like(depth)
     bn, fh, fw, c = feat_nhwc.shape
@@ -450,7 +462,7 @@ class _MGHSPool(torch.autograd.Function):
         dev = depth.device
         shapes = [tuple(t.shape) for t in _alloc_shapes(plan, layout)]
         gdt = ctx.out_dtype if all(g is None or g.dtype == ctx.out_dtype for g in grads) else torch.float32
-        gs = [torch.zeros(s, dtype=gdt, device=dev) if g is None else g.to(gdt).contiguous() for g, s in zip(grads, shapes)]
+        gs = [torch.zeros(s, dtype=gdt, device=dev) if g is None else _lib.dense16(g.to(gdt)) for g, s in zip(grads, shapes)]
         arr = _views(plan, layout, gs)
         bn, fh, fw, c = feat_nhwc.shape
         with torch.cuda.device(dev):

@@ -71,7 +71,7 @@ class _AttentionStage(torch.autograd.Function):
         b, c, hw = ctx.dims
         dev = x.device
         st = _lib.stream_ptr(dev)
-        go = go.float().contiguous()
+        go = _lib.dense16(go.float())   # any view of a gradient -> dense and aligned, as forward does with x
         with torch.cuda.device(dev):
             gx = torch.empty_like(x)
             gs2 = torch.empty_like(s2d)
@@ -237,7 +237,7 @@ class _FusedStage(torch.autograd.Function):
         b, c, hw = ctx.dims
         dev = x.device
         lib = _lib.load()
-        go = go.to(ctx.io_dtype).contiguous()
+        go = _lib.dense16(go.to(ctx.io_dtype))   # a sliced / expanded / offset gradient is copied, as _stage_input does with x
         with torch.cuda.device(dev):
             gx = torch.empty(x.shape, dtype=ctx.io_dtype, device=dev)
             gps = [torch.empty_like(p) for p in ps]

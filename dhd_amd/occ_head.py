@@ -49,10 +49,14 @@ def occ_head_infer(x, w1, b1, w2, b2, dz=16, labels=None, mask_camera=None, hist
     layout = _layout_of(x)
     if layout is None:
         x, layout = x.contiguous(), 0
+    if x.data_ptr() % 16:     # 16-byte loads of x: a dense view at an odd storage offset is copied, in its layout
+        x = x.clone(memory_format=torch.preserve_format)
     b, c, dy, dx = x.shape
     if hist is not None and labels is None:
         raise _lib.DhdError('occ_head_infer: hist needs labels (nothing would be counted)')
     w1, b1, w2, b2 = _f32(w1, 'predicter[0].weight'), _f32(b1, 'predicter[0].bias'), _f32(w2, 'predicter[2].weight'), _f32(b2, 'predicter[2].bias')
+    if b2.data_ptr() % 16:    # read as float4; a parameter that is a view of a flat buffer may sit anywhere
+        b2 = b2.clone()
     n_cls = w2.shape[0] // dz
     if w1.shape[1] != c or b1.numel() != w1.shape[0] or w2.shape != (dz * n_cls, w1.shape[0]) or b2.numel() != w2.shape[0]:
         raise _lib.DhdError('occ_head_infer: inconsistent parameter shapes')
@@ -73,6 +77,9 @@ def occ_head_infer(x, w1, b1, w2, b2, dz=16, labels=None, mask_camera=None, hist
         if labels is not None:
             lab = labels.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
             msk = None if mask_camera is None else mask_camera.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
+            # labels and mask are read 8 voxels at a time
+            lab = lab.clone() if lab.data_ptr() % 8 else lab
+            msk = msk.clone() if msk is not None and msk.data_ptr() % 8 else msk
             if lab.numel() != pred.numel() or (msk is not None and msk.numel() != pred.numel()):
                 raise _lib.DhdError('occ_head_infer: labels / mask_camera must have one element per voxel')
             if hist is None:

@@ -153,7 +153,7 @@ class _WindowRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, H, W, ws, sh, reverse, out_dtype):
-        x = x.contiguous()
+        x = _lib.dense16(x)     # also the incoming gradient of backward, which re-enters here
         B, C = x.shape[0], x.shape[-1]
         nh, nw = -(-H // ws), -(-W // ws)
         shape = (B, H, W, C) if reverse else (B, nh * nw, ws * ws, C)

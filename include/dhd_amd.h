@@ -11,6 +11,10 @@
  *   - Return value: 0 on success, a positive hipError_t if a launch failed, or one of the
  *     negative DHD_E* codes for argument errors.  (The reference validates nothing and
  *     returns void: ops/bev_pool_v2/src/bev_pool.cpp:30-57.)
+ *   - Alignment: a [dev] tensor is dense (no strides; the caller copies a view) and aligned to its element size.  Where the
+ *     kernels of an entry point move a tensor in 16-byte vectors, the function says so below and a misaligned pointer is
+ *     refused on the host with DHD_EINVAL before any launch; entry points that say nothing access single elements (or pick a
+ *     scalar kernel for a misaligned pointer themselves) and take any element-aligned address.
  *   - Floating point data is float32 and indices int32, exactly as in the reference
  *     (ops/bev_pool_v2/bev_pool.py:19-25), unless an argument says otherwise: since ABI 3 the large tensors at the
  *     edges of the MGHS and SFA operators may be float16 / bfloat16 (dhd_tensor_view.dtype, dhd_sfa_weights.io_dtype),
@@ -140,7 +144,8 @@ typedef struct dhd_mghs_desc {
  *       dhd_mghs_forward is then bit-identical from run to run, and equal to a sum in ascending ranks_depth order.  The
  *       backward is deterministic either way.
  *   DHD_MGHS_FEAT_GRAD_NCHW  dhd_mghs_backward* write the context gradient as (B*N, C, fH, fW) -- the layout of the
- *       reference's tran_feat -- instead of (B*N, fH, fW, C), so that the caller needs no transposition pass. */
+ *       reference's tran_feat -- instead of (B*N, fH, fW, C), so that the caller needs no transposition pass.
+ *   (Off the compact path -- C != 64 -- the backward adds into feat_grad with float atomics: its last bits vary from run to run.) */
 #define DHD_MGHS_DETERMINISTIC 1
 #define DHD_MGHS_FEAT_GRAD_NCHW 2
 #define DHD_MGHS_DEBUG_SCAN_SELF_SERVE 4 /* tests only: the single-pass scan never waits for another workgroup (its bounded-spin fallback for every chunk) */
@@ -191,7 +196,8 @@ int dhd_height_band(const float* height /*[dev]*/, int bn, int n_height, int fh,
                     uint8_t* band /*[dev] (B*N,fH,fW)*/, void* stream);
 
 /* (B*N, C, fH, fW) -> (B*N, fH, fW, C) and back (the reference's feat.permute(0,1,3,4,2) at
- * lss_heightmap.py:290, made contiguous at bev_pool.py:21). */
+ * lss_heightmap.py:290, made contiguous at bev_pool.py:21).  Any alignment: 16-byte vectors where both tensors are 16-byte aligned
+ * and c, hw are multiples of 4, single elements otherwise (dhd_mghs_lift's re-layout likewise). */
 int dhd_feat_nchw_to_nhwc(const float* src, float* dst, int bn, int c, int hw, void* stream);
 int dhd_feat_nhwc_to_nchw(const float* src, float* dst, int bn, int c, int hw, void* stream);
 
@@ -227,7 +233,10 @@ int dhd_mghs_lift_static(const dhd_mghs_desc* desc, const dhd_calib* calib, cons
  * out[g] is the FINAL reference layout (B, nz_g*C, ny_g, nx_g) with channel = z*C + c, i.e. the
  * result of bev_pool.py:105 (permute) followed by lss_heightmap.py:298-299 (collapse_z); the same
  * memory viewed as (B, nz_g, C, ny_g, nx_g) serves collapse_z=False.  Every element is written
- * (zeros included); no pre-zeroing needed.  Uses the scratch part of `ws` (per-voxel sums). */
+ * (zeros included); no pre-zeroing needed.  Uses the scratch part of `ws` (per-voxel sums).
+ * Alignment (every dhd_mghs_forward... / dhd_mghs_backward... entry point): out[g] / out_grad[g], plain or as views, are moved in
+ * 16-byte vectors and must be 16-byte aligned; on the compact path (C = 64, ny % 4 == 0, nx % 4 == 0) so are feat_nhwc and
+ * feat_grad.  DHD_EINVAL otherwise, before any launch.  depth / depth_grad are accessed by element. */
 int dhd_mghs_forward(const dhd_mghs_desc* desc, const float* depth, const float* feat_nhwc,
                      float* const out[DHD_MAX_GRIDS], const dhd_mghs_workspace* ws, void* stream);
 
@@ -314,6 +323,9 @@ int dhd_hbm_calibrate(void* buf /*[dev]*/, size_t bytes, int pattern, void* stre
  * 3. SFA channel/spatial attention stage (models/necks/mix.py:37-59), memory-bound parts.
  *    x is (B, 2C, H, W): channels [0,C) = x_bev, [C,2C) = x_voxel.
  * ------------------------------------------------------------------------------------ */
+
+/* Alignment (this section): any.  The kernels move float4 where hw % 4 == 0 AND every (B, *, H, W) tensor of the call is 16-byte
+ * aligned, single floats otherwise. */
 
 /* fea_S = x.mean(-1).mean(-1)  (mix.py:41) -> s (B, 2C). */
 int dhd_sfa_channel_mean(const float* x, float* s, int b, int c2, int hw, void* stream);
@@ -421,6 +433,9 @@ size_t dhd_sfa_stage_scratch_bytes(int b, int c, int hw, int hidden);
 /* The same two sizes for a given dhd_sfa_weights.storage_dtype (ABI 4; DHD_F32 gives the values above). */
 int dhd_sfa_stage_workspace_bytes(int b, int c, int hw, int hidden, int storage_dtype, size_t* saved_bytes, size_t* scratch_bytes);
 
+/* Alignment (every dhd_sfa_stage_... entry point that takes them): x, out, gout, gx, saved and scratch are moved in 16-byte vectors
+ * and must be 16-byte aligned, DHD_EINVAL otherwise, checked before the first launch.  The parameters, running statistics and
+ * parameter gradients are read and written by element (4-byte aligned); sync_sums 8-byte aligned. */
 /* x (B,2C,H,W) -> out (B,C,H,W) = x_fuse of mix.py:58.  x is float32, or w->storage_dtype when that is a half type. */
 int dhd_sfa_stage_forward(const void* x, const dhd_sfa_weights* w, void* out /* w->io_dtype */, void* saved,
                           void* scratch, int b, int c, int hw, void* stream);
@@ -560,7 +575,8 @@ int dhd_deform_col2im(const float* dcol, const float* x, const float* offset, fl
  * land in (they are shared by all channels), then every cell sums its own list from LDS-staged dcol rows -- no atomics
  * (csrc/deform.hip).  `workspace`: dhd_deform_col2im_workspace_bytes(b, h, w, k) bytes of device scratch, 16-byte aligned,
  * owned by the caller.  Shapes the gather form does not take (dhd_deform_col2im_gather_supported == 0: k*k*h*w elements of
- * `col_dtype` must fit 144 KiB of LDS) return DHD_EUNSUPPORTED; dhd_deform_col2im covers them in float32. */
+ * `col_dtype` must fit 144 KiB of LDS) return DHD_EUNSUPPORTED; dhd_deform_col2im covers them in float32.
+ * Alignment: any (x, offset, col, dx, doffset by element; dcol rows in 16-byte vectors only where dcol is 16-byte aligned). */
 int dhd_deform_im2col_t(const void* x, int x_dtype, const float* offset, void* col, int col_dtype,
                         int b, int c, int h, int w, int k, int pad, int dil, void* stream);
 size_t dhd_deform_col2im_workspace_bytes(int b, int h, int w, int k);
@@ -578,6 +594,7 @@ int dhd_deform_col2im_t(const void* dcol, int col_dtype, const void* x, int x_dt
  *      argmax(height) (0 / 1 / 2, 255 none; NULL: not wanted), from the float32 height_range[h_bins] / mask_range[4] as
  *      dhd_height_band.  The softmax is torch's for this shape, operation for operation (max, sum of expf, correctly rounded
  *      division, bins in order): the same bits as `x.float().softmax(1)` on the GPU.
+ * Alignment: any (every access is a single element; a dense view at an odd storage offset is read where it lies).
  * backward: g_depth / g_feat / g_height (float32 NCHW, any of them NULL = zero) -> g_xd (bn, ct, hw) in xd's dtype and layout
  * (softmax Jacobian on the first d channels, g_feat on the next c, zeros beyond) and g_hl (bn, ht, hw) likewise; either output
  * may be NULL.  Nothing is allocated; the caller's stream. */
@@ -605,7 +622,9 @@ int dhd_points_to_maps(const float* points, int n_cams, int n_points, int height
  * holds the normalised sampling positions of F.grid_sample(align_corners=True, padding zeros), as the
  * reference's gen_grid produces them.  cost = sum_c |curr - sample(prev)|, + bias where the sample of
  * channel flag_channel (the reference's last group, C-4) is exactly 0; out (bn, n_depth, h, w) =
- * softmax over the depth hypotheses of -cost.  c % 4 == 0, c <= 1024, n_depth <= 256.  No gradient. */
+ * softmax over the depth hypotheses of -cost.  c % 4 == 0, c <= 1024, n_depth <= 256.  No gradient.
+ * Alignment: prev_nhwc and curr_nhwc 16 bytes (a pixel's channels move in 16-byte groups), grid 8 bytes (one float2 per sample);
+ * DHD_EINVAL before the launch otherwise.  out by element. */
 int dhd_stereo_cost_volume(const float* prev_nhwc, const float* curr_nhwc, const float* grid, int bn,
                            int c, int h, int w, int n_depth, float bias, int flag_channel, float* out,
                            void* stream);
@@ -634,6 +653,8 @@ int dhd_ema_update_dev(const uint64_t* ema_addr, const uint64_t* model_addr, con
  *    2 bfloat16); parameters, statistics and gradients of the parameters float32; gamma / beta /
  *    running_* / dgamma / dbeta may be NULL.  hw must be a multiple of 4 (float32) or 8 elements and
  *    n*c <= 65535 (dhd_bn_supported).  save_mean / save_rstd carry the batch statistics to backward.
+ *    Alignment: x, y, grad_y, grad_x (9b: also residual, grad_residual) are moved in 16-byte vectors and must be 16-byte
+ *    aligned (DHD_EINVAL before any launch); parameters, statistics and the workspace by element.
  * ------------------------------------------------------------------------------------ */
 int dhd_bn_supported(int dtype, int n, int c, int hw);
 size_t dhd_bn_workspace_bytes(int n, int c, int hw);
@@ -672,6 +693,8 @@ int dhd_bn_nhwc_train_backward(const void* x, const void* y, const void* grad_y,
  *     1: (n, h, w, c) channels_last with c a multiple of 4 (float32) / 8 elements; dtype as in section 9;
  *     hout >= hin, wout >= win, factors up to 8.  Index arithmetic as torch's UpSample.cuh (float32);
  *     backward is a gather: one writer per element, float32 accumulation, deterministic.
+ *     Alignment: layout 1 moves rows of channels in 16-byte vectors: x, y, grad_y, grad_x 16-byte aligned (DHD_EINVAL otherwise).
+ *     Layout 0 accesses single elements: aligned to the element size.
  * ------------------------------------------------------------------------------------ */
 int dhd_upsample_bilinear_supported(int dtype, int layout, int n, int c, int hin, int win, int hout, int wout);
 int dhd_upsample_bilinear_forward(const void* x, int dtype, int layout, int n, int c, int hin, int win,
@@ -683,6 +706,7 @@ int dhd_upsample_bilinear_backward(const void* grad_y, int dtype, int layout, in
  * 11. Layout conversion at the boundary between the NCHW operators above and dense stacks that run in
  *     channels_last: batched transpose in[b][rows][cols] -> out[b][cols][rows] of 2- or 4-byte elements
  *     (NCHW -> NHWC: rows = c, cols = h*w; NHWC -> NCHW: rows = h*w, cols = c).  in and out must not overlap.
+ *     Alignment: 4 bytes (4-byte elements; 2-byte elements with even rows and cols move as 4-byte pairs), else 2; DHD_EINVAL otherwise.
  * ------------------------------------------------------------------------------------ */
 int dhd_transpose_batched(const void* in, void* out, int elem_bytes, long batch, int rows, int cols, void* stream);
 
@@ -692,6 +716,7 @@ int dhd_transpose_batched(const void* in, void* out, int elem_bytes, long batch,
  *     (b, nh*nw, window*window, c) with nh = ceil(h / window), nw = ceil(w / window); reverse = 0: partition (padding rows
  *     are zeros), 1: reverse (padding rows dropped).  c a multiple of 8; in / out dtypes as in section 9 and may differ
  *     (float32 LayerNorm output -> autocast dtype; half gradients -> float32).  Each direction is the other's transpose.
+ *     Alignment: rows move in 16-byte vectors: in and out 16-byte aligned (DHD_EINVAL before the launch).
  * ------------------------------------------------------------------------------------ */
 int dhd_window_rows(const void* in, void* out, int in_dtype, int out_dtype, int b, int h, int w, int c, int window,
                     int shift, int reverse, void* stream);

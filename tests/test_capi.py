@@ -277,6 +277,83 @@ def test_workspace_alignment_is_checked_on_the_host():
     assert lib.dhd_mghs_prepare(C.byref(d), C.byref(cal), None, C.byref(ws), None) == -2
 
 
+def test_tensor_alignment_is_checked_on_the_host():
+    """Every entry point whose kernels move a caller's tensor as 16-byte vectors (csrc/vec16.h; 4-byte pairs in layout.hip) refuses a
+    misaligned pointer with DHD_EINVAL before any launch: fake addresses, no device touched.  Each call is otherwise valid, and
+    where a later host check exists the same call with the aligned address reaches it (-3), so the -1 is the alignment test's."""
+    from dhd_amd import _lib
+    lib = _lib.load()
+    P, M = C.c_void_p(0x10000), C.c_void_p(0x10004)     # 16-byte aligned / 4 bytes off
+    H = C.c_void_p(0x10002)                             # 2 bytes off: a one-element offset of a half tensor
+
+    def each(fn, args, slots, later=None):
+        """fn(*args) with the pointer at each of `slots` replaced by a misaligned one -> -1; `later`: (slot, value, code) of a
+        host check behind the alignment test that the aligned call reaches."""
+        for s in slots:
+            for bad in (M, H):
+                a = list(args)
+                a[s] = bad
+                assert fn(*a) == -1, (fn.__name__, s, bad.value)
+        if later is not None:
+            a = list(args)
+            a[later[0]] = later[1]
+            assert fn(*a) == later[2], fn.__name__
+            a[slots[0]] = M
+            assert fn(*a) == -1, fn.__name__
+
+    # SFA stage: x, out, saved, scratch / gout, gx (the parameters are read element by element)
+    w, g = _lib.SfaWeights(), _lib.SfaGrads()
+    for f, _ in _lib.SfaWeights._fields_[:16]:
+        setattr(w, f, 0x20000)
+    for f, _ in _lib.SfaGrads._fields_:
+        setattr(g, f, 0x20000)
+    w.hidden = 16
+    S = C.c_void_p(0x30000)   # sync_sums
+    each(lib.dhd_sfa_stage_forward, [P, C.byref(w), P, P, P, 2, 128, 64, None], (0, 2, 3, 4), later=(6, 64, -3))
+    each(lib.dhd_sfa_stage_backward, [P, C.byref(w), P, P, P, C.byref(g), P, 2, 128, 64, None], (0, 2, 3, 4, 6), later=(8, 64, -3))
+    each(lib.dhd_sfa_stage_forward_phase, [P, C.byref(w), P, P, P, 2, 128, 64, 2, S, None], (0, 2, 3, 4), later=(6, 64, -3))
+    each(lib.dhd_sfa_stage_backward_phase, [P, C.byref(w), P, P, P, C.byref(g), P, 2, 128, 64, 2, S, None], (0, 2, 3, 4, 6), later=(8, 64, -3))
+    each(lib.dhd_sfa_stage_infer, [P, C.byref(w), P, P, 2, 128, 64, 0, None], (0, 2, 3), later=(5, 64, -3))
+    # BatchNorm, NCHW and channels_last: x, y, grad_y, grad_x, residual, grad_residual
+    each(lib.dhd_bn_train_forward, [P, 0, 2, 8, 64, None, None, None, None, 0.1, 1e-5, P, P, P, P, None], (0, 11), later=(1, 3, -3))
+    each(lib.dhd_bn_train_backward, [P, P, 0, 2, 8, 64, None, P, P, P, None, None, P, None], (0, 1, 9), later=(2, 3, -3))
+    each(lib.dhd_bn_nhwc_train_forward, [P, P, 0, 128, 8, 2, None, None, None, None, 0.1, 1e-5, P, P, P, P, P, None], (0, 1, 12),
+         later=(2, 3, -3))
+    each(lib.dhd_bn_nhwc_train_backward, [P, P, P, 0, 128, 8, 2, None, P, P, P, P, P, None, None, P, None], (0, 1, 2, 11, 12),
+         later=(3, 3, -3))
+    # bilinear up-sampling: channels_last rows are vectors; the NCHW kernels are scalar and take any element-aligned address
+    each(lib.dhd_upsample_bilinear_forward, [P, 0, 1, 1, 8, 4, 4, 8, 8, P, None], (0, 9), later=(1, 3, -3))
+    each(lib.dhd_upsample_bilinear_backward, [P, 0, 1, 1, 8, 4, 4, 8, 8, P, None], (0, 9), later=(1, 3, -3))
+    assert lib.dhd_upsample_bilinear_forward(M, 0, 0, 1, 8, 4, 4, 2, 8, M, None) == -3     # NCHW float32 at 4 bytes off: passes on to the
+    assert lib.dhd_upsample_bilinear_forward(H, 1, 0, 1, 8, 4, 4, 2, 8, H, None) == -3     # shape check (down-sampling); half at 2 bytes too
+    assert lib.dhd_upsample_bilinear_forward(H, 0, 0, 1, 8, 4, 4, 8, 8, P, None) == -1     # float32 at 2 bytes off
+    # window partition / reverse
+    each(lib.dhd_window_rows, [P, P, 0, 2, 1, 7, 7, 8, 7, 0, 0, None], (0, 1), later=(7, 12, -3))
+    # layout: 4-byte elements and the 2-byte pair kernel (even rows and cols) need 4-byte alignment; the scalar 2-byte kernel does not
+    for eb, rows, cols, bad in ((4, 7, 9, H), (2, 8, 10, H)):
+        assert lib.dhd_transpose_batched(bad, P, eb, 0, rows, cols, None) == -1 and lib.dhd_transpose_batched(P, bad, eb, 0, rows, cols, None) == -1
+        assert lib.dhd_transpose_batched(P, P, eb, 0, rows, cols, None) == -3              # (batch 0: the check behind it)
+    assert lib.dhd_transpose_batched(H, H, 2, 0, 7, 10, None) == -3                        # odd rows: element accesses only
+    # stereo cost volume: 16-byte channel groups of prev / curr, one float2 per sampling position
+    each(lib.dhd_stereo_cost_volume, [P, P, P, 2, 16, 6, 10, 8, 5.0, 12, P, None], (0, 1), later=(4, 18, -3))
+    assert lib.dhd_stereo_cost_volume(P, P, M, 2, 16, 6, 10, 8, 5.0, 12, P, None) == -1
+    # MGHS on the compact path (C = 64): a context row and the pooled tensors move as 16-byte vectors
+    d = _lib.MghsDesc()
+    d.batch, d.n_cams, d.n_depth, d.fh, d.fw, d.channels, d.n_grids = 1, 1, 4, 4, 11, 64, 1
+    d.grid[0].n[0], d.grid[0].n[1], d.grid[0].n[2] = 8, 8, 1
+    n, m = C.c_size_t(0), C.c_size_t(0)
+    assert lib.dhd_mghs_workspace_bytes(C.byref(d), C.byref(n), C.byref(m)) == 0
+    ws = _lib.MghsWorkspace(0x100000, n.value, 0x4000000, m.value)
+    good, bad = (C.c_void_p * _lib.DHD_MAX_GRIDS)(0x8000000), (C.c_void_p * _lib.DHD_MAX_GRIDS)(0x8000004)
+    assert lib.dhd_mghs_forward_gather(C.byref(d), P, M, C.byref(ws), None) == -1
+    assert lib.dhd_mghs_forward(C.byref(d), P, M, C.byref(good), C.byref(ws), None) == -1
+    assert lib.dhd_mghs_forward_stream(C.byref(d), P, M, C.byref(good), C.byref(ws), None) == -1
+    assert lib.dhd_mghs_forward_stream(C.byref(d), P, P, C.byref(bad), C.byref(ws), None) == -1
+    assert lib.dhd_mghs_backward(C.byref(d), P, M, C.byref(good), P, P, C.byref(ws), None) == -1
+    assert lib.dhd_mghs_backward(C.byref(d), P, P, C.byref(good), P, M, C.byref(ws), None) == -1
+    assert lib.dhd_mghs_backward(C.byref(d), P, P, C.byref(bad), P, P, C.byref(ws), None) == -1
+
+
 def _build_c_example(tmp_path):
     """examples/capi_kat.c with plain gcc (C11): the header is C, the only other dependency is the HIP runtime's host API."""
     exe = str(tmp_path / 'capi_kat')
