@@ -180,6 +180,9 @@ _PROTOTYPES = {
     'dhd_occ_head_infer_supported': ([_I] * 7, _I),
     'dhd_occ_head_infer_scratch_bytes': ([C.POINTER(OccHeadWeights), _I, C.POINTER(C.c_size_t)], _I),
     'dhd_occ_head_infer': ([_P, _I, _I, C.POINTER(OccHeadWeights), _I, _I, _I] + [_P] * 7, _I),
+    'dhd_deform_conv_infer_supported': ([_I] * 9, _I),
+    'dhd_deform_conv_infer_scratch_bytes': ([_I] * 9 + [C.POINTER(C.c_size_t)], _I),
+    'dhd_deform_conv_infer': ([_P, _I, _I, _P, _P, _P] + [_I] * 10 + [_P, C.c_size_t, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -213,6 +216,11 @@ def check(rc, what):
     if rc < 0:
         raise DhdError(f'{what}: {_ERRORS.get(rc, rc)}')
     raise DhdError(f'{what}: hipError_t {rc}')
+
+
+def call(name, *args):
+    """Entry point `name` of the library with `args`; a non-zero return code raises DhdError."""
+    check(getattr(load(), name)(*args), name)
 
 
 def stream_ptr(device=None):

@@ -20,6 +20,7 @@
 // im2col emits half and the two backward kernels read the half gradient (155 MB -> 78 MB per pass at the DHD-S size, and
 // no cast kernels in between); x is read, and its gradient written, as float32 or in the column type; the offsets and their
 // gradient are float32, arithmetic is float32.
+#include "deform_tap.h"
 #include "vec16.h"
 
 namespace {
@@ -32,40 +33,9 @@ __device__ __forceinline__ size_t x_at(int b, int ch, int i, int c, int hw) { re
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return (T)v; }   // round to nearest even
 
-struct Tap {
-  int i00, i01, i10, i11;   // flat indices into the H*W plane (valid ones only are used)
-  float w00, w01, w10, w11; // bilinear weights, 0 for corners outside the image
-  float ly, lx;             // fractional parts
-  bool v00, v01, v10, v11, inside;
-};
-
-__device__ __forceinline__ Tap make_tap(float py, float px, int h, int w) {
-  Tap t;
-  t.inside = py > -1.0f && px > -1.0f && py < (float)h && px < (float)w;
-  const float fy = floorf(py), fx = floorf(px);
-  const int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
-  t.ly = py - fy;
-  t.lx = px - fx;
-  const float hy = 1.0f - t.ly, hx = 1.0f - t.lx;
-  t.v00 = t.inside && y0 >= 0 && x0 >= 0;
-  t.v01 = t.inside && y0 >= 0 && x1 <= w - 1;
-  t.v10 = t.inside && y1 <= h - 1 && x0 >= 0;
-  t.v11 = t.inside && y1 <= h - 1 && x1 <= w - 1;
-  t.i00 = y0 * w + x0; t.i01 = y0 * w + x1; t.i10 = y1 * w + x0; t.i11 = y1 * w + x1;
-  t.w00 = t.v00 ? hy * hx : 0.f;
-  t.w01 = t.v01 ? hy * t.lx : 0.f;
-  t.w10 = t.v10 ? t.ly * hx : 0.f;
-  t.w11 = t.v11 ? t.ly * t.lx : 0.f;
-  return t;
-}
-
-__device__ __forceinline__ Tap tap_of(const float* __restrict__ off_b, int t, int p, int h, int w, int k, int pad, int dil) {
-  const int hw = h * w;
-  const int y = p / w, x = p % w, ky = t / k, kx = t % k;
-  const float py = (float)(y + ky * dil - pad) + off_b[(size_t)(2 * t) * hw + p];
-  const float px = (float)(x + kx * dil - pad) + off_b[(size_t)(2 * t + 1) * hw + p];
-  return make_tap(py, px, h, w);
-}
+using dhd_deform::Tap;       // deform_tap.h: shared with deform_conv.hip
+using dhd_deform::make_tap;
+using dhd_deform::tap_of;
 
 template <typename TC, typename TX>
 __global__ __launch_bounds__(kBlock) void deform_im2col(const TX* __restrict__ x, const float* __restrict__ off,

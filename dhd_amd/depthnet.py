@@ -97,6 +97,11 @@ class DCN(nn.Module):
     below is the same math for CPU tensors and serves as the cross-check in the tests."""
 
     use_hip = True
+    # Opt-in (dhd_amd.fused_inference): in eval mode with nothing to differentiate, forward runs the fused operator of
+    # deform_conv.py (csrc/deform_conv.hip) where it takes the layer: no column matrix, no staging copy of x.  Off by default:
+    # its float32 result (bf16x3) is within the layer's bar but not bit-identical to the rocBLAS product, and the height logits
+    # behind it feed an argmax.
+    fused_infer = False
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1,
                  deform_groups=1, im2col_step=128, bias=False):
@@ -113,7 +118,26 @@ class DCN(nn.Module):
         nn.init.zeros_(self.conv_offset.weight)
         nn.init.zeros_(self.conv_offset.bias)
 
+    def fused_applies(self, x):
+        """True when forward runs the fused inference operator on `x`; otherwise today's path (im2col + matmul) runs."""
+        if not (self.fused_infer and not self.training and torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        from .deform_conv import deform_conv_infer_supported
+        probe = torch.empty((0,) + tuple(x.shape[1:]), dtype=self._compute_dtype(), device=x.device)
+        return deform_conv_infer_supported(probe, self.weight, self.groups)
+
+    @staticmethod
+    def _compute_dtype():
+        cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else torch.float32
+        return cdt if cdt in (torch.float16, torch.bfloat16) else torch.float32
+
     def forward(self, x):
+        if self.fused_infer and self.fused_applies(x):
+            from .deform_conv import deform_conv_infer
+            out = deform_conv_infer(x.to(self._compute_dtype()), self.conv_offset(x), self.weight, self.padding, self.dilation, self.groups)
+            return out.contiguous()     # dense NCHW in the compute dtype, what the matmul below hands on
         b, c, h, w = x.shape
         k = self.k
         g = self.groups

@@ -797,6 +797,45 @@ int dhd_occ_head_infer(const void* x, int x_dtype, int layout, const dhd_occ_hea
                        uint8_t* pred, float* logits, const uint8_t* labels, const uint8_t* mask, int64_t* hist,
                        void* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------ *
+ * 15. Deformable convolution at inference (the `DCN` of HeightNet / DepthNet, section 7): sampling and the grouped
+ *     product with the layer's weight in one kernel,
+ *       out[b, o, p] = sum over the c of o's group and the 9 taps t of  weight[o, c, t] * bilinear(x[b, c], position of (t, p)),
+ *     with the sampling arithmetic of dhd_deform_im2col_t (float32: integer base + offset, zero outside the image).  The
+ *     column matrix (b, c_in * 9, h * w) of section 7 never exists in memory.  Forward only; additive to ABI 6.
+ *     Supported (dhd_deform_conv_infer_supported: 1 / 0): k = 3 (stride 1, one deformable group, no bias); c_in / groups and
+ *     c_out / groups each a multiple of 8 in [8, 128]; c_in * h * w and c_out * h * w below 2^31; x float32, float16 or
+ *     bfloat16 in layout 0 (b, c_in, h, w) or 1 (channels_last: (b, h, w, c_in) in memory), the codes of sections 10 and 14.
+ *     The call itself takes any pad >= 0 and dil >= 1 and any b with b * c * h * w < 2^31 for c = c_in, c_out and 18.
+ *     Arithmetic: float32 x -- sampled values and weights each cut into two exact bf16 parts, three bf16 MFMA products per
+ *     a*b (DHD_SFA_GEMM_BF16X3 = DHD_SFA_GEMM_DEFAULT; the other codes unsupported).  Half x -- the sampled value rounded
+ *     once to x's type (what dhd_deform_im2col_t writes into a half column matrix), the weights rounded once to it, one
+ *     f16 / bf16 MFMA product (gemm must be DHD_SFA_GEMM_DEFAULT).  Accumulation is float32; no atomics, the summation
+ *     order is fixed: two calls on the same inputs give the same bytes.
+ * ------------------------------------------------------------------------------------ */
+int dhd_deform_conv_infer_supported(int c_in, int c_out, int groups, int k, int h, int w, int x_dtype, int layout, int gemm);
+
+/* Bytes of `scratch` for one call (a multiple of 16):
+ *   round_up(groups * ceil(9 * (c_in / groups) / 16) * ceil((c_out / groups) / 32) * P * 1024, 256)      P = 2 for float32 x, else 1
+ *   + (layout == 0 ? round_up(b * c_in * h * w * sizeof(element of x), 16) : 0)
+ * the weights in the order and number format the kernel consumes them, and the channels_last copy of an NCHW x (made by the
+ * kernel of section 11).  Both are rewritten by every call; nothing is kept between calls or process-wide.  DHD_EINVAL for
+ * bytes == NULL, a non-positive size, a bad dtype / layout code or c % groups != 0; DHD_EUNSUPPORTED for an unsupported shape. */
+int dhd_deform_conv_infer_scratch_bytes(int b, int c_in, int c_out, int groups, int k, int h, int w, int x_dtype, int layout,
+                                        size_t* bytes);
+
+/* x [dev] (b, c_in, h, w) in x_dtype and `layout`; offset [dev] float32 dense (b, 18, h, w), channel 2t = dy and 2t+1 = dx of
+ * tap t (section 7); weight [dev] float32 (c_out, c_in / groups, 3, 3), the parameter as it lies; out [dev] (b, c_out, h, w)
+ * in x's dtype and layout, every element written.  x, out and scratch 16-byte aligned (corner runs, the weight stream and
+ * a channels_last out move as 16-byte vectors); offset and weight are read element by element and take any 4-byte aligned
+ * address.  No pointer may be NULL except `stream`.  Every argument is checked on the host before the first launch: NULL,
+ * non-positive sizes, pad < 0, dil < 1, a bad dtype / layout / gemm code, c % groups != 0 or a misaligned pointer ->
+ * DHD_EINVAL; an unsupported shape or precision -> DHD_EUNSUPPORTED; scratch_bytes below the size above -> DHD_ENOSPACE.
+ * Two launches on `stream` for a channels_last x (weight stream, operator), three for NCHW (the transpose in between). */
+int dhd_deform_conv_infer(const void* x, int x_dtype, int layout, const float* offset, const float* weight, void* out,
+                          int b, int c_in, int c_out, int groups, int h, int w, int k, int pad, int dil, int gemm,
+                          void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
