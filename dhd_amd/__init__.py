@@ -18,6 +18,7 @@ from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noq
 from .amp_weights import HalfWeightCache  # noqa: F401
 from .occ_head import occ_head_infer  # noqa: F401
 from .deform_conv import deform_conv_infer, deform_conv_infer_supported  # noqa: F401
+from .window_attn import window_attn_infer, window_attn_infer_supported  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'
@@ -25,11 +26,14 @@ __version__ = '0.1.0'
 
 def fused_inference(model, enabled=True):
     """The one switch for the inference operators whose results are within their bars but not bit-identical to the module
-    formulation: sets `fused_infer` on every occupancy head (`predictor`) and every `DCN` of `model` and returns the modules it
-    switched.  They take their fused operator only in eval mode with nothing to differentiate, and only where it has the shape."""
+    formulation: sets `fused_infer` on every occupancy head (`predictor`), every `DCN` and every Swin `WindowMSA` of `model` and
+    returns the modules it switched.  They take their fused operator only in eval mode with nothing to differentiate, and only
+    where it has the shape (window attention: head dimension 32, at most 144 tokens per window; under autocast it keeps the
+    relative-position bias in float32 where the module formulation rounds it to the half type)."""
     from .depthnet import DCN
     from .detector import predictor
-    switched = [m for m in model.modules() if isinstance(m, (DCN, predictor))]
+    from .swin import WindowMSA
+    switched = [m for m in model.modules() if isinstance(m, (DCN, predictor, WindowMSA))]
     for m in switched:
         m.fused_infer = bool(enabled)
     return switched

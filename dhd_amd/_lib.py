@@ -183,6 +183,8 @@ _PROTOTYPES = {
     'dhd_deform_conv_infer_supported': ([_I] * 9, _I),
     'dhd_deform_conv_infer_scratch_bytes': ([_I] * 9 + [C.POINTER(C.c_size_t)], _I),
     'dhd_deform_conv_infer': ([_P, _I, _I, _P, _P, _P] + [_I] * 10 + [_P, C.c_size_t, _P], _I),
+    'dhd_window_attn_infer_supported': ([_I] * 6, _I),
+    'dhd_window_attn_infer': ([_P, _I, _P, _P, _P] + [_I] * 6 + [C.c_float, _I, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

@@ -116,13 +116,48 @@ class WindowMSA(nn.Module):
     def init_weights(self):
         nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
 
-    def forward(self, x, mask=None):
-        """x: (B, nW, N, C) windows; mask: (nW, N, N) additive shift mask or None."""
+    # Opt-in (dhd_amd.fused_inference): in eval mode with nothing to differentiate, the attention between the two Linear layers
+    # runs as the one operator of window_attn.py (csrc/window_attn.hip) where it has the shape.  Off by default: its result is
+    # within the layer's bar but not bit-identical to SDPA, and under autocast it keeps the bias in float32.
+    fused_infer = False
+
+    def _fused_conditions(self, x, mask, regions):
+        """The conditions of the routed branch that need no look at the qkv tensor."""
+        if not (self.fused_infer and not self.training and torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        if mask is not None and regions is None:
+            return False
+        if regions is not None and not (regions.is_cuda and regions.dtype == torch.uint8 and tuple(regions.shape) == tuple(x.shape[1:3])):
+            return False
+        return self.embed_dims == 32 * self.num_heads and x.shape[-1] == self.embed_dims
+
+    def fused_applies(self, x, mask=None, regions=None):
+        """True when forward runs the fused inference operator on windows `x` (B, nW, N, C); otherwise today's path runs.  forward
+        itself asks the library once, about the qkv tensor it has made."""
+        if not self._fused_conditions(x, mask, regions):
+            return False
+        from .window_attn import window_attn_shape_supported
+        cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype
+        return x.shape[2] == self.window_size[0] * self.window_size[1] and \
+            window_attn_shape_supported(self.window_size, self.num_heads, cdt, 3 * x.numel())
+
+    def forward(self, x, mask=None, regions=None):
+        """x: (B, nW, N, C) windows; mask: (nW, N, N) additive shift mask or None; regions: the uint8 (nW, N) region ids the mask
+        was made from (shift_window_regions), which the fused inference operator reads instead of the mask."""
         B, nW, N, C = x.shape
         nh = self.num_heads
+        qkv = self.qkv(x)
+        if self.fused_infer and self._fused_conditions(x, mask, regions):
+            from .window_attn import window_attn_infer, window_attn_infer_supported
+            if window_attn_infer_supported(qkv, self.window_size, nh):     # the one question to the library, about the actual qkv
+                out = window_attn_infer(qkv, self.relative_position_bias_table, self.window_size, nh, self.scale,
+                                        regions if mask is not None else None)
+                return self.proj_drop(self.proj(out))
         # windows x heads as the "head" axis of a 4-D attention call: the additive term (nW * heads, N, N) is then
         # shared by the whole batch without being copied per image, and the fused attention kernels apply
-        qkv = self.qkv(x).view(B, nW, N, 3, nh, C // nh).permute(3, 0, 1, 4, 2, 5).reshape(3, B, nW * nh, N, C // nh)
+        qkv = qkv.view(B, nW, N, 3, nh, C // nh).permute(3, 0, 1, 4, 2, 5).reshape(3, B, nW * nh, N, C // nh)
         bias = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(N, N, -1).permute(2, 0, 1)
         bias = bias.unsqueeze(0).expand(nW, nh, N, N) if mask is None else bias.unsqueeze(0) + mask.unsqueeze(1)
         out = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=bias.reshape(1, nW * nh, N, N).to(qkv.dtype),
@@ -131,16 +166,22 @@ class WindowMSA(nn.Module):
         return self.proj_drop(self.proj(out.transpose(2, 3).reshape(B, nW, N, C)))
 
 
-def shift_window_mask(H_pad, W_pad, window, shift, device):
-    """swin.py:420-447: windows that straddle the cyclic seam must not attend across it (-100 between regions)."""
-    img = torch.zeros(H_pad, W_pad, device=device)
+def shift_window_regions(H_pad, W_pad, window, shift, device):
+    """uint8 (nW, N): the region id (0..8) of every token of every window of the cyclically shifted, padded map (swin.py:420-441);
+    tokens of different regions of a window come from opposite sides of the seam."""
+    img = torch.zeros(H_pad, W_pad, dtype=torch.uint8, device=device)
     cuts = (slice(0, -window), slice(-window, -shift), slice(-shift, None))
     for i, hs in enumerate(cuts):
         for j, ws in enumerate(cuts):
             img[hs, ws] = 3 * i + j
-    win = img.view(H_pad // window, window, W_pad // window, window).permute(0, 2, 1, 3).reshape(-1, window * window)
-    diff = win.unsqueeze(1) - win.unsqueeze(2)
-    return torch.where(diff != 0, torch.full_like(diff, -100.0), torch.zeros_like(diff))
+    return img.view(H_pad // window, window, W_pad // window, window).permute(0, 2, 1, 3).reshape(-1, window * window).contiguous()
+
+
+def shift_window_mask(H_pad, W_pad, window, shift, device):
+    """swin.py:420-447: windows that straddle the cyclic seam must not attend across it (-100 between regions)."""
+    win = shift_window_regions(H_pad, W_pad, window, shift, device)
+    differ = win.unsqueeze(1) != win.unsqueeze(2)
+    return torch.where(differ, torch.full(differ.shape, -100.0, device=device), torch.zeros(differ.shape, device=device))
 
 
 _PLAIN_WINDOWS = bool(__import__('os').environ.get('DHD_PLAIN_WINDOWS'))   # A/B switch: F.pad + torch.roll + permute copies
@@ -194,7 +235,7 @@ class ShiftWindowMSA(nn.Module):
         if _windows_on_gpu(x):
             # the same data movement as below in two launches instead of six copies (csrc/window.hip); under autocast the
             # windows leave in the dtype the qkv projection casts its input to, and come back in the projection's dtype
-            mask = None
+            mask = regions = None
             if sh > 0:
                 key = (H + pad_b, W + pad_r, ws, sh, x.device)
                 if masks is None:
@@ -203,9 +244,17 @@ class ShiftWindowMSA(nn.Module):
                     if key not in masks:
                         masks[key] = shift_window_mask(H + pad_b, W + pad_r, ws, sh, x.device)
                     mask = masks[key]
+                if self.w_msa.fused_infer:      # the ids the mask was made from, for the fused inference operator
+                    rkey = ('regions',) + key
+                    if masks is None:
+                        regions = shift_window_regions(H + pad_b, W + pad_r, ws, sh, x.device)
+                    else:
+                        if rkey not in masks:
+                            masks[rkey] = shift_window_regions(H + pad_b, W + pad_r, ws, sh, x.device)
+                        regions = masks[rkey]
             odt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() and x.dtype == torch.float32 else x.dtype
             win = _WindowRows.apply(x, H, W, ws, sh, False, odt)
-            win = self.w_msa(win, mask)
+            win = self.w_msa(win, mask) if regions is None else self.w_msa(win, mask, regions=regions)
             x = _WindowRows.apply(win, H, W, ws, sh, True, win.dtype)
             return self.drop(x.view(B, H * W, C))
         if pad_r or pad_b:

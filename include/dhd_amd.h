@@ -836,6 +836,37 @@ int dhd_deform_conv_infer(const void* x, int x_dtype, int layout, const float* o
                           int b, int c_in, int c_out, int groups, int h, int w, int k, int pad, int dil, int gemm,
                           void* scratch, size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------ *
+ * 16. Swin window attention at inference (`WindowMSA` between its two Linear layers): from the qkv projection's output, as it
+ *     lies, to the tensor `proj` reads, in one launch.  With yi = i / ww, xi = i % ww, N = wh * ww and q / k / v the three
+ *     (nh, 32) slices of a token's qkv row,
+ *       out[w, i, 32 h + c] = sum_j softmax_j( scale * sum_c q[w, i, h, c] k[w, j, h, c]
+ *                                              + table[(yi - yj + wh - 1) (2 ww - 1) + (xi - xj + ww - 1), h]
+ *                                              - 100 * [regions[w % nw, i] != regions[w % nw, j]] ) * v[w, j, h, c].
+ *     The -100 is additive (never -inf); with regions == NULL that term is absent.  The scores, the probabilities, the
+ *     expanded bias / mask and the permuted q / k / v never reach memory; no scratch buffer, nothing allocated, kept or
+ *     synchronised.  Forward only; additive to ABI 6.
+ *     Supported (dhd_window_attn_infer_supported: 1 / 0): head_dim = 32; wh, ww >= 1 with N <= 144; nh >= 1; float32, float16
+ *     or bfloat16; N * 3 * nh * 32 < 2^31 (the call: windows * N * 3 * nh * 32 < 2^31).
+ *     Arithmetic: both products on v_mfma_f32_16x16x32_{f16,bf16}; softmax maxima, sums and all accumulation in float32.  Half
+ *     qkv -- one product per a*b, the exponentials rounded once to qkv's type and divided by their float32 sum afterwards
+ *     (gemm must be DHD_SFA_GEMM_DEFAULT).  float32 qkv -- q, k, v and the exponentials each cut into two bf16 parts, three
+ *     products per a*b (DHD_SFA_GEMM_BF16X3 = DHD_SFA_GEMM_DEFAULT; the other codes unsupported).  The summation order is
+ *     fixed: two calls on the same inputs give the same bytes.
+ * ------------------------------------------------------------------------------------ */
+int dhd_window_attn_infer_supported(int wh, int ww, int nh, int head_dim, int dtype, int gemm);
+
+/* qkv [dev] dense (windows, N, 3, nh, 32) in `dtype`: the memory of the qkv Linear's output for x (B, nw, N, nh * 32),
+ * windows = B * nw; table [dev] float32 ((2 wh - 1)(2 ww - 1), nh), the relative_position_bias_table as it lies; regions [dev]
+ * uint8 (nw, N), the region id of every token of every window of the shifted map, or NULL; out [dev] dense
+ * (windows, N, nh * 32) in qkv's dtype, every element written.  N is padded to a multiple of 16 inside the kernel only: padded
+ * keys have weight exactly 0, padded rows are neither loaded nor stored, nothing outside qkv and out is touched.
+ * qkv and out 16-byte aligned, table 4-byte aligned; regions by element.  Checked on the host before the launch: NULL qkv /
+ * table / out, non-positive sizes, windows % nw != 0, a bad dtype / gemm code or a misaligned pointer -> DHD_EINVAL; an
+ * unsupported shape or precision -> DHD_EUNSUPPORTED.  One launch on `stream`. */
+int dhd_window_attn_infer(const void* qkv, int dtype, const float* table, const uint8_t* regions, void* out, int windows, int nw,
+                          int wh, int ww, int nh, int head_dim, float scale, int gemm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
