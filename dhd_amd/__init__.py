@@ -18,7 +18,8 @@ from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noq
 from .amp_weights import HalfWeightCache  # noqa: F401
 from .occ_head import occ_head_infer  # noqa: F401
 from .deform_conv import deform_conv_infer, deform_conv_infer_supported  # noqa: F401
-from .window_attn import window_attn_infer, window_attn_infer_supported  # noqa: F401
+from . import window_attn  # noqa: F401  (the module, callable as its function window_attn)
+from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'
@@ -36,4 +37,17 @@ def fused_inference(model, enabled=True):
     switched = [m for m in model.modules() if isinstance(m, (DCN, predictor, WindowMSA))]
     for m in switched:
         m.fused_infer = bool(enabled)
+    return switched
+
+
+def fused_training(model, on=True):
+    """The training sibling of fused_inference: sets `fused_train` on every Swin `WindowMSA` of `model` and returns the modules it
+    switched.  With it the attention between the two Linear layers runs as `window_attn` -- the fused forward on qkv as it lies
+    and its fused HIP backward -- in train and eval mode, with or without grad, wherever the operator has the shape (head
+    dimension 32, at most 144 tokens per window, a GPU tensor) and attention dropout is inactive; every other call keeps SDPA.
+    Within the layer's bar of SDPA, not bit-identical; under autocast the relative-position bias and its gradient stay float32."""
+    from .swin import WindowMSA
+    switched = [m for m in model.modules() if isinstance(m, WindowMSA)]
+    for m in switched:
+        m.fused_train = bool(on)
     return switched

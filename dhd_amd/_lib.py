@@ -185,6 +185,9 @@ _PROTOTYPES = {
     'dhd_deform_conv_infer': ([_P, _I, _I, _P, _P, _P] + [_I] * 10 + [_P, C.c_size_t, _P], _I),
     'dhd_window_attn_infer_supported': ([_I] * 6, _I),
     'dhd_window_attn_infer': ([_P, _I, _P, _P, _P] + [_I] * 6 + [C.c_float, _I, _P], _I),
+    'dhd_window_attn_backward_supported': ([_I] * 6, _I),
+    'dhd_window_attn_backward_scratch_bytes': ([_I] * 4, C.c_size_t),
+    'dhd_window_attn_backward': ([_P, _P, _I, _P, _P, _P, _P, _P, C.c_size_t] + [_I] * 6 + [C.c_float, _I, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -223,6 +226,11 @@ def check(rc, what):
 def call(name, *args):
     """Entry point `name` of the library with `args`; a non-zero return code raises DhdError."""
     check(getattr(load(), name)(*args), name)
+
+
+def value(name, *args):
+    """Entry point `name` of the library where it returns a value rather than an error code (`*_supported`, `*_bytes`)."""
+    return getattr(load(), name)(*args)
 
 
 def stream_ptr(device=None):

@@ -7,6 +7,7 @@ follow the reference (`patch_embed.projection`, `stages.i.blocks.j.attn.w_msa.qk
 window attention goes through `F.scaled_dot_product_attention` with one additive term (relative-position
 bias + shift mask) instead of materialised score matrices, and the shift masks are built once per feature
 map size instead of in every block's forward (swin.py:420-447 rebuilds them 24x per image)."""
+import os
 import warnings
 from collections import OrderedDict
 
@@ -121,12 +122,23 @@ class WindowMSA(nn.Module):
     # within the layer's bar but not bit-identical to SDPA, and under autocast it keeps the bias in float32.
     fused_infer = False
 
-    def _fused_conditions(self, x, mask, regions):
-        """The conditions of the routed branch that need no look at the qkv tensor."""
-        if not (self.fused_infer and not self.training and torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+    # Opt-in (dhd_amd.fused_training, or DHD_WINDOW_ATTN_TRAIN=1 in the environment so that a whole training step can be A/B'd):
+    # the same operator with its HIP backward (window_attn.window_attn, csrc/window_attn_bwd.hip), in train and eval mode, with
+    # or without grad, wherever it has the shape and attention dropout is inactive.  Off by default for the same reason.
+    fused_train = bool(os.environ.get('DHD_WINDOW_ATTN_TRAIN'))
+
+    def _fused_conditions(self, x, mask, regions, train=False):
+        """The conditions of a routed branch (inference, or training with train=True) that need no look at the qkv tensor."""
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
             return False
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            return False
+        if train:
+            if not self.fused_train or (self.training and self.attn_drop.p > 0):
+                return False
+        else:
+            if not (self.fused_infer and not self.training):
+                return False
+            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+                return False
         if mask is not None and regions is None:
             return False
         if regions is not None and not (regions.is_cuda and regions.dtype == torch.uint8 and tuple(regions.shape) == tuple(x.shape[1:3])):
@@ -145,7 +157,7 @@ class WindowMSA(nn.Module):
 
     def forward(self, x, mask=None, regions=None):
         """x: (B, nW, N, C) windows; mask: (nW, N, N) additive shift mask or None; regions: the uint8 (nW, N) region ids the mask
-        was made from (shift_window_regions), which the fused inference operator reads instead of the mask."""
+        was made from (shift_window_regions), which the fused operator (inference or training) reads instead of the mask."""
         B, nW, N, C = x.shape
         nh = self.num_heads
         qkv = self.qkv(x)
@@ -154,6 +166,12 @@ class WindowMSA(nn.Module):
             if window_attn_infer_supported(qkv, self.window_size, nh):     # the one question to the library, about the actual qkv
                 out = window_attn_infer(qkv, self.relative_position_bias_table, self.window_size, nh, self.scale,
                                         regions if mask is not None else None)
+                return self.proj_drop(self.proj(out))
+        if self.fused_train and self._fused_conditions(x, mask, regions, train=True):
+            from .window_attn import window_attn, window_attn_supported
+            if window_attn_supported(qkv, self.window_size, nh):          # asked once, about the actual qkv
+                out = window_attn(qkv, self.relative_position_bias_table, self.window_size, nh, self.scale,
+                                  regions if mask is not None else None)
                 return self.proj_drop(self.proj(out))
         # windows x heads as the "head" axis of a 4-D attention call: the additive term (nW * heads, N, N) is then
         # shared by the whole batch without being copied per image, and the fused attention kernels apply
@@ -244,7 +262,7 @@ class ShiftWindowMSA(nn.Module):
                     if key not in masks:
                         masks[key] = shift_window_mask(H + pad_b, W + pad_r, ws, sh, x.device)
                     mask = masks[key]
-                if self.w_msa.fused_infer:      # the ids the mask was made from, for the fused inference operator
+                if self.w_msa.fused_infer or self.w_msa.fused_train:      # the ids the mask was made from, for the fused operator
                     rkey = ('regions',) + key
                     if masks is None:
                         regions = shift_window_regions(H + pad_b, W + pad_r, ws, sh, x.device)

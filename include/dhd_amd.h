@@ -867,6 +867,44 @@ int dhd_window_attn_infer_supported(int wh, int ww, int nh, int head_dim, int dt
 int dhd_window_attn_infer(const void* qkv, int dtype, const float* table, const uint8_t* regions, void* out, int windows, int nw,
                           int wh, int ww, int nh, int head_dim, float scale, int gemm, void* stream);
 
+/* ------------------------------------------------------------------------------------ *
+ * 17. Backward of section 16, for training: dhd_window_attn_infer is the training forward too and saves nothing but its
+ *     inputs.  With S_ij the score inside the softmax of section 16, P = softmax_j(S) and dout the gradient of `out`,
+ *       dP_ij = sum_c dout[w, i, 32 h + c] v[w, j, h, c]        delta_i = sum_j P_ij dP_ij        dS_ij = P_ij (dP_ij - delta_i)
+ *       dq[w, i, h, :] = scale sum_j dS_ij k[w, j, h, :]    dk[w, j, h, :] = scale sum_i dS_ij q[w, i, h, :]
+ *       dv[w, j, h, :] = sum_i P_ij dout[w, i, 32 h + :]
+ *       dtable[r, h]   = sum over w and all (i, j) with (yi - yj + wh - 1) (2 ww - 1) + (xi - xj + ww - 1) = r of dS_ij.
+ *     dqkv holds dq / dk / dv where qkv holds q / k / v: it is the gradient the qkv Linear consumes, with no permute back.
+ *     The scores and the softmax statistics are recomputed; neither `out` nor a log-sum-exp is read.  Same support table,
+ *     limits and precisions as section 16 (float32: two bf16 parts per operand, three products per a * b, also for P and dS;
+ *     half: one product, P and dS rounded once to qkv's type, dq / dk / dv rounded once at the end; softmax, delta and dS in
+ *     float32).  dtable is accumulated and stored in float32 from the unrounded dS in every precision.
+ *     Reproducibility: dqkv is written without atomics in a fixed summation order -- two calls on the same inputs give the same
+ *     bytes.  dtable is accumulated per workgroup with LDS float atomics (no global atomics; the per-workgroup partial rows in
+ *     `scratch` are then added in a fixed order by a second launch), so its low bits are NOT reproducible from run to run.
+ *     dq on the one hand and dk / dv on the other are built from two evaluations of P: the scores are computed once as K Q^T and
+ *     once as Q K^T, and in float32 (three bf16 products, the cross terms in the other order) exp(S - max) can differ in its
+ *     last bits between the two, so sum_j P_ij of the second evaluation is 1 only to float32 rounding.  Inside the 1e-4 bar.
+ *     Additive to ABI 6.
+ * ------------------------------------------------------------------------------------ */
+int dhd_window_attn_backward_supported(int wh, int ww, int nh, int head_dim, int dtype, int gemm);
+
+/* Bytes of caller-provided scratch (the dtable partial rows) for a call with these sizes; non-decreasing in `windows`; 0 for
+ * sizes the operator does not take. */
+size_t dhd_window_attn_backward_scratch_bytes(int windows, int wh, int ww, int nh);
+
+/* qkv, table, regions, windows .. gemm as in dhd_window_attn_infer; dout [dev] dense (windows, N, nh * 32) in qkv's dtype, the
+ * gradient of the tensor `proj` reads, as it lies; dqkv [dev] dense, qkv's shape, dtype and layout, every element written;
+ * dtable [dev] float32 ((2 wh - 1)(2 ww - 1), nh), every element written (not accumulated into); scratch [dev] of at least
+ * dhd_window_attn_backward_scratch_bytes bytes, contents undefined before and after.  Nothing else is touched; the inputs are
+ * only read.  qkv, dout and dqkv 16-byte aligned; table, dtable and scratch 4-byte aligned; regions by element.  Checked on the
+ * host before the first launch: a NULL pointer other than regions / stream, non-positive sizes, windows % nw != 0, a bad dtype
+ * / gemm code or a misaligned pointer -> DHD_EINVAL; an unsupported shape or precision, or windows * N * 3 * nh * 32 >= 2^31
+ * -> DHD_EUNSUPPORTED; scratch_bytes too small -> DHD_ENOSPACE.  Two launches on `stream`; nothing allocated or synchronised. */
+int dhd_window_attn_backward(const void* qkv, const void* dout, int dtype, const float* table, const uint8_t* regions, void* dqkv,
+                             float* dtable, void* scratch, size_t scratch_bytes, int windows, int nw, int wh, int ww, int nh,
+                             int head_dim, float scale, int gemm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
