@@ -1027,20 +1027,26 @@ def _fresh_run(row, gpu, v, const, monkeypatch):
 
 def test_the_table_covers_every_function_that_hands_a_pointer_to_the_library():
     """Every function of dhd_amd/ that passes a tensor pointer to the library (`_lib.ptr(` or `.data_ptr()` next to a library
-    call) belongs to an operator with a row here; the C entry points the rows watch are the checkable form of that."""
+    call) belongs to an operator with a row here; the C entry points the rows watch are the checkable form of that.  The
+    spellings of a library call: `lib.dhd_x(`, `load().dhd_x(`, `_call('dhd_x'`, `_lib.call('dhd_x'` and `_lib.value('dhd_x'`."""
     import re
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'dhd_amd')
     called = set()
     for f in os.listdir(root):
         if f.endswith('.py') and f != '_lib.py':
             called |= set(re.findall(r'\b(?:lib|load\(\))\.(dhd_[a-z0-9_]+)', open(os.path.join(root, f)).read()))
-            called |= set(re.findall(r"_call\('(dhd_[a-z0-9_]+)'", open(os.path.join(root, f)).read()))
+            called |= set(re.findall(r"(?:_call|\bcall|\bvalue)\(\s*'(dhd_[a-z0-9_]+)'", open(os.path.join(root, f)).read()))
     launching = {n for n in called if not n.endswith(('_supported', '_bytes')) and n != 'dhd_abi_version'}
+    assert {'dhd_window_attn_infer', 'dhd_window_attn_backward', 'dhd_deform_conv_infer'} <= launching      # the _lib.call spelling is seen
     watched = {e for row in ROWS for e in row.watch}
     # not operators on caller tensors: calibration stream of bench.py, test-only introspection, graph-capture twin of dhd_ema_update,
     # the cross-rank phases of the SFA stage (two ranks: test_fused_sfa_stage_under_syncbatchnorm_two_ranks), static-rig lift
     exempt = {'dhd_hbm_calibrate', 'dhd_mghs_debug_keys', 'dhd_mghs_stats', 'dhd_ema_update_dev', 'dhd_sfa_stage_forward_phase',
               'dhd_sfa_stage_backward_phase', 'dhd_mghs_lift_static', 'dhd_bev_pool_v2_regroup', 'dhd_deform_col2im', 'dhd_deform_im2col'}
+    # shown on views by a test of their own, which carves the tensor out of a poisoned parent with present() as the rows here do
+    exempt |= {'dhd_deform_conv_infer',        # test_gpu_deform_conv_infer.py::test_views
+               'dhd_window_attn_backward',     # test_gpu_window_attn_train.py::test_a_strided_or_misaligned_dout_is_copied
+               'dhd_window_attn_infer'}        # test_gpu_window_attn_infer.py::test_views_of_qkv
     assert launching - watched - exempt == set(), sorted(launching - watched - exempt)
 
 
