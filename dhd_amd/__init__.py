@@ -20,6 +20,7 @@ from .occ_head import occ_head_infer  # noqa: F401
 from .deform_conv import deform_conv_infer, deform_conv_infer_supported  # noqa: F401
 from . import window_attn  # noqa: F401  (the module, callable as its function window_attn)
 from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
+from .swin_glue import layer_norm_rows, window_reverse_add, swin_glue_supported  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'
@@ -50,4 +51,18 @@ def fused_training(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, WindowMSA)]
     for m in switched:
         m.fused_train = bool(on)
+    return switched
+
+
+def fused_swin_glue(model, on=True):
+    """Sets `fused_glue` on every `SwinBlock` of `model` and returns the blocks it switched.  With it a block's LayerNorms, window
+    partition / reverse, DropPath and first residual add run as the operators of swin_glue.py (norm1 into the windows, reverse +
+    add, norm2 into the dtype fc1 reads) wherever the windows are cut on the GPU, both norms are affine over the channels and
+    the channel count is a multiple of 8 up to 2048; every other call keeps today's path.  The attention inside the windows and
+    its own switches (fused_inference, fused_training) are untouched.  Within the layer's bar of torch's LayerNorm, not
+    bit-identical; the random stream of an active DropPath is unchanged."""
+    from .swin import SwinBlock
+    switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
+    for m in switched:
+        m.fused_glue = bool(on)
     return switched

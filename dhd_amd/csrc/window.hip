@@ -6,27 +6,13 @@
 //   reverse  : out[b][y][x][:] = win[b][wy][wx][iy][ix][:] with (wy ws + iy, wx ws + ix) = ((y - shift) mod Hp, (x - shift) mod Wp)
 // Each is also the other's transpose (the gradient of one is the other applied to the gradient).  The element type may change on the
 // way (float32 LayerNorm output -> the autocast dtype the qkv projection would cast to anyway; half gradients -> float32).
-#include "vec16.h"
+#include "window_geom.h"
 
 namespace {
 
+using dhd::WinGeom;
+
 constexpr int kWinBlock = 256;
-
-// eight consecutive elements <-> float registers, as 16-byte accesses
-template <typename T> __device__ __forceinline__ void load8(const T* p, float (&v)[8]) {
-  using V = dhd::Vec16<T, false>;
-#pragma unroll
-  for (int k = 0; k < 8; k += V::N) V::load(p + k, v + k);
-}
-template <typename T> __device__ __forceinline__ void store8(T* p, const float (&v)[8]) {
-  using V = dhd::Vec16<T, false>;
-#pragma unroll
-  for (int k = 0; k < 8; k += V::N) V::store(p + k, v + k);
-}
-
-struct WinGeom {
-  int b, h, w, c, ws, shift, hp, wp, nh, nw;
-};
 
 // one thread per (row, group of 8 channels); rows of the OUTPUT are walked in order, the source row comes from the index map
 template <typename TI, typename TO, bool REVERSE>
@@ -37,33 +23,15 @@ __global__ __launch_bounds__(kWinBlock) void window_rows(const TI* __restrict__ 
   for (long idx = (long)blockIdx.x * kWinBlock + threadIdx.x; idx < total; idx += (long)gridDim.x * kWinBlock) {
     const int cg = (int)(idx % groups);
     const long row = idx / groups;
-    long src;   // source row, -1 = zeros
-    if (REVERSE) {
-      const int x = (int)(row % g.w), y = (int)((row / g.w) % g.h);
-      const long bi = row / ((long)g.w * g.h);
-      int py = y - g.shift, px = x - g.shift;
-      if (py < 0) py += g.hp;
-      if (px < 0) px += g.wp;
-      src = (((bi * g.nh + py / g.ws) * g.nw + px / g.ws) * g.ws + py % g.ws) * g.ws + px % g.ws;
-    } else {
-      const int ws2 = g.ws * g.ws;
-      const int i = (int)(row % ws2);
-      const long win = row / ws2;
-      const int wx = (int)(win % g.nw), wy = (int)((win / g.nw) % g.nh);
-      const long bi = win / ((long)g.nw * g.nh);
-      int y = wy * g.ws + i / g.ws + g.shift, x = wx * g.ws + i % g.ws + g.shift;
-      if (y >= g.hp) y -= g.hp;
-      if (x >= g.wp) x -= g.wp;
-      src = (y < g.h && x < g.w) ? (bi * g.h + y) * g.w + x : -1;
-    }
+    const long src = REVERSE ? dhd::win_reverse_src(g, row) : dhd::win_partition_src(g, row);   // source row, -1 = zeros
     float v[8];
     if (src < 0) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = 0.f;
     } else {
-      load8<TI>(in + src * g.c + cg * 8, v);
+      dhd::load8<TI>(in + src * g.c + cg * 8, v);
     }
-    store8<TO>(out + row * g.c + cg * 8, v);
+    dhd::store8<TO>(out + row * g.c + cg * 8, v);
   }
 }
 
@@ -87,11 +55,7 @@ extern "C" int dhd_window_rows(const void* in, void* out, int in_dtype, int out_
   if (in_dtype < 0 || in_dtype > 2 || out_dtype < 0 || out_dtype > 2 || b <= 0 || h <= 0 || w <= 0 || c <= 0 || (c & 7) || window <= 0 ||
       shift < 0 || shift >= window)
     return DHD_EUNSUPPORTED;
-  WinGeom g{b, h, w, c, window, shift, 0, 0, 0, 0};
-  g.nh = (h + window - 1) / window;
-  g.nw = (w + window - 1) / window;
-  g.hp = g.nh * window;
-  g.wp = g.nw * window;
+  const WinGeom g = dhd::win_geom(b, h, w, c, window, shift);
   if ((long)b * g.hp * g.wp >= (1L << 40)) return DHD_EUNSUPPORTED;
   hipStream_t st = dhd_stream(stream);
   return dhd::with_dtype<dhd::HipHalf>(in_dtype, [&](auto* ti) {

@@ -244,6 +244,29 @@ class ShiftWindowMSA(nn.Module):
         self.w_msa = WindowMSA(embed_dims, num_heads, _pair(window_size), qkv_bias, qk_scale, attn_drop_rate, proj_drop_rate)
         self.drop = DropPath(drop_path)
 
+    def _shift_mask(self, Hp, Wp, device, masks):
+        """(mask, regions) of the padded Hp x Wp map for the windows-on-GPU path: the additive shift mask (None without a shift),
+        and the region ids it was made from where a fused attention operator is switched on; both cached in `masks` when given."""
+        ws, sh = self.window_size, self.shift_size
+        mask = regions = None
+        if sh > 0:
+            key = (Hp, Wp, ws, sh, device)
+            if masks is None:
+                mask = shift_window_mask(Hp, Wp, ws, sh, device)
+            else:
+                if key not in masks:
+                    masks[key] = shift_window_mask(Hp, Wp, ws, sh, device)
+                mask = masks[key]
+            if self.w_msa.fused_infer or self.w_msa.fused_train:      # the ids the mask was made from, for the fused operator
+                rkey = ('regions',) + key
+                if masks is None:
+                    regions = shift_window_regions(Hp, Wp, ws, sh, device)
+                else:
+                    if rkey not in masks:
+                        masks[rkey] = shift_window_regions(Hp, Wp, ws, sh, device)
+                    regions = masks[rkey]
+        return mask, regions
+
     def forward(self, query, hw_shape, masks=None):
         B, L, C = query.shape
         H, W = hw_shape
@@ -253,23 +276,7 @@ class ShiftWindowMSA(nn.Module):
         if _windows_on_gpu(x):
             # the same data movement as below in two launches instead of six copies (csrc/window.hip); under autocast the
             # windows leave in the dtype the qkv projection casts its input to, and come back in the projection's dtype
-            mask = regions = None
-            if sh > 0:
-                key = (H + pad_b, W + pad_r, ws, sh, x.device)
-                if masks is None:
-                    mask = shift_window_mask(H + pad_b, W + pad_r, ws, sh, x.device)
-                else:
-                    if key not in masks:
-                        masks[key] = shift_window_mask(H + pad_b, W + pad_r, ws, sh, x.device)
-                    mask = masks[key]
-                if self.w_msa.fused_infer or self.w_msa.fused_train:      # the ids the mask was made from, for the fused operator
-                    rkey = ('regions',) + key
-                    if masks is None:
-                        regions = shift_window_regions(H + pad_b, W + pad_r, ws, sh, x.device)
-                    else:
-                        if rkey not in masks:
-                            masks[rkey] = shift_window_regions(H + pad_b, W + pad_r, ws, sh, x.device)
-                        regions = masks[rkey]
+            mask, regions = self._shift_mask(H + pad_b, W + pad_r, x.device, masks)
             odt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() and x.dtype == torch.float32 else x.dtype
             win = _WindowRows.apply(x, H, W, ws, sh, False, odt)
             win = self.w_msa(win, mask) if regions is None else self.w_msa(win, mask, regions=regions)
@@ -311,7 +318,41 @@ class SwinBlock(nn.Module):
         self.norm2 = nn.LayerNorm(embed_dims)
         self.ffn = FFN(embed_dims, feedforward_channels, drop_rate, drop_path_rate)
 
+    # Opt-in (dhd_amd.fused_swin_glue, or DHD_SWIN_GLUE=1 in the environment so that a whole training step can be A/B'd): what
+    # the block does to the token map outside its Linear layers and its attention runs as the operators of swin_glue.py
+    # (csrc/swin_glue.hip) -- norm1 into the window partition, window reverse + DropPath + residual add, norm2 into the dtype
+    # fc1 reads.  Off by default: the LayerNorm statistics are within the layer's bar of torch's, not its bits.
+    fused_glue = bool(os.environ.get('DHD_SWIN_GLUE'))
+
+    def _glue_applies(self, x):
+        """True when forward takes the fused route for the tokens x (B, L, C)."""
+        from .swin_glue import swin_glue_supported
+        C = x.shape[-1]
+        affine = all(n.elementwise_affine and n.bias is not None and tuple(n.normalized_shape) == (C,) for n in (self.norm1, self.norm2))
+        return x.dim() == 3 and _windows_on_gpu(x) and affine and swin_glue_supported(x)
+
+    def _forward_glue(self, x, hw_shape, masks):
+        from .swin_glue import layer_norm_rows, swin_glue_supported, window_reverse_add
+        attn = self.attn
+        (H, W), ws, sh = hw_shape, attn.window_size, attn.shift_size
+        mask, regions = attn._shift_mask(-(-H // ws) * ws, -(-W // ws) * ws, x.device, masks)
+        cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype     # what qkv / fc1 cast their input to
+        win = layer_norm_rows(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, cdt, (H, W, ws, sh))
+        win = attn.w_msa(win, mask) if regions is None else attn.w_msa(win, mask, regions=regions)
+        scale = None
+        if attn.drop.training and attn.drop.drop_prob != 0.:
+            # DropPath.forward's draw, call for call (the RNG stream does not change), as the per-image factor of the add
+            keep = 1 - attn.drop.drop_prob
+            kept = keep + torch.rand((x.shape[0],) + (1,) * (x.dim() - 1), dtype=win.dtype, device=win.device)
+            scale = kept.floor().float().div(keep).view(-1)
+        x = window_reverse_add(win, x, H, W, ws, sh, scale)
+        if not swin_glue_supported(x, plain_ln_to=cdt):      # a small map and no cast to fuse: torch's LayerNorm, as today
+            return self.ffn(self.norm2(x), identity=x)
+        return self.ffn(layer_norm_rows(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, cdt), identity=x)
+
     def forward(self, x, hw_shape, masks=None):
+        if self.fused_glue and self._glue_applies(x):
+            return self._forward_glue(x, hw_shape, masks)
         x = x + self.attn(self.norm1(x), hw_shape, masks)
         return self.ffn(self.norm2(x), identity=x)
 
