@@ -21,6 +21,7 @@ from .deform_conv import deform_conv_infer, deform_conv_infer_supported  # noqa:
 from . import window_attn  # noqa: F401  (the module, callable as its function window_attn)
 from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
 from .swin_glue import layer_norm_rows, window_reverse_add, swin_glue_supported  # noqa: F401
+from .swin_ffn import swin_ffn_infer, swin_ffn_supported  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'
@@ -31,7 +32,8 @@ def fused_inference(model, enabled=True):
     formulation: sets `fused_infer` on every occupancy head (`predictor`), every `DCN` and every Swin `WindowMSA` of `model` and
     returns the modules it switched.  They take their fused operator only in eval mode with nothing to differentiate, and only
     where it has the shape (window attention: head dimension 32, at most 144 tokens per window; under autocast it keeps the
-    relative-position bias in float32 where the module formulation rounds it to the half type)."""
+    relative-position bias in float32 where the module formulation rounds it to the half type).  The second half of a Swin block
+    has a switch of its own, `fused_swin_ffn`, which this one does not set."""
     from .depthnet import DCN
     from .detector import predictor
     from .swin import WindowMSA
@@ -65,4 +67,18 @@ def fused_swin_glue(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
     for m in switched:
         m.fused_glue = bool(on)
+    return switched
+
+
+def fused_swin_ffn(model, on=True):
+    """Sets `fused_ffn` on every `SwinBlock` of `model` and returns the blocks it switched.  With it the second half of a block --
+    norm2, fc1, GELU, fc2 and the residual add -- runs as the one operator of swin_ffn.py in eval mode with nothing to
+    differentiate, wherever the operator has the shape (C = 128 or 256 with mlp_ratio 4, a GPU tensor, two biased Linear layers
+    around an exact GELU, an affine norm2) and the measurement routed that size and dtype to it (swin_ffn.ROUTED); every other
+    call keeps today's path bit for bit.  It is a switch of its own and not part of fused_inference; it composes with
+    fused_inference and fused_swin_glue.  Within the layer's bar of the module formulation, not bit-identical."""
+    from .swin import SwinBlock
+    switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
+    for m in switched:
+        m.fused_ffn = bool(on)
     return switched

@@ -324,6 +324,40 @@ class SwinBlock(nn.Module):
     # fc1 reads.  Off by default: the LayerNorm statistics are within the layer's bar of torch's, not its bits.
     fused_glue = bool(os.environ.get('DHD_SWIN_GLUE'))
 
+    # Opt-in (dhd_amd.fused_swin_ffn, or DHD_SWIN_FFN=1 in the environment): in eval mode with nothing to differentiate, the
+    # second half of the block -- norm2, fc1, GELU, fc2 and the residual add -- runs as the one operator of swin_ffn.py
+    # (csrc/swin_ffn.hip) where it has the shape and the measurement routed it (swin_ffn.ROUTED).  Off by default: within the
+    # layer's bar of the module formulation, not its bits.  Composes with fused_glue and the attention's fused_infer.
+    fused_ffn = bool(os.environ.get('DHD_SWIN_FFN'))
+
+    def _ffn_applies(self, x):
+        """True when the block's second half runs as swin_ffn_infer on the tokens x (..., C); otherwise today's path runs."""
+        if not (self.fused_ffn and not self.training and torch.is_tensor(x) and x.is_cuda):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in (*self.norm2.parameters(), *self.ffn.parameters()))):
+            return False
+        # the reference structure: two Linear layers with biases, exact GELU, an affine norm2 over C (dropout is inactive in eval)
+        n, L = self.norm2, self.ffn.layers
+        C = x.shape[-1]
+        if not (isinstance(n, nn.LayerNorm) and n.elementwise_affine and n.bias is not None and tuple(n.normalized_shape) == (C,)):
+            return False
+        if not (len(L) == 3 and isinstance(L[0], nn.Sequential) and len(L[0]) == 3 and isinstance(L[0][0], nn.Linear)
+                and isinstance(L[0][1], nn.GELU) and L[0][1].approximate == 'none' and isinstance(L[1], nn.Linear)
+                and L[0][0].bias is not None and L[1].bias is not None and L[0][0].in_features == C and L[1].out_features == C
+                and L[1].in_features == L[0][0].out_features):
+            return False
+        from .swin_ffn import swin_ffn_supported
+        return swin_ffn_supported(x, L[0][0].out_features, torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
+
+    def _ffn_half(self, x):
+        """x + ffn(norm2(x)): the fused operator where _ffn_applies, else None."""
+        if not (self.fused_ffn and self._ffn_applies(x)):
+            return None
+        from .swin_ffn import swin_ffn_infer
+        fc1, fc2 = self.ffn.layers[0][0], self.ffn.layers[1]
+        return swin_ffn_infer(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                              torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
+
     def _glue_applies(self, x):
         """True when forward takes the fused route for the tokens x (B, L, C)."""
         from .swin_glue import swin_glue_supported
@@ -346,6 +380,9 @@ class SwinBlock(nn.Module):
             kept = keep + torch.rand((x.shape[0],) + (1,) * (x.dim() - 1), dtype=win.dtype, device=win.device)
             scale = kept.floor().float().div(keep).view(-1)
         x = window_reverse_add(win, x, H, W, ws, sh, scale)
+        out = self._ffn_half(x)
+        if out is not None:
+            return out
         if not swin_glue_supported(x, plain_ln_to=cdt):      # a small map and no cast to fuse: torch's LayerNorm, as today
             return self.ffn(self.norm2(x), identity=x)
         return self.ffn(layer_norm_rows(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, cdt), identity=x)
@@ -354,6 +391,9 @@ class SwinBlock(nn.Module):
         if self.fused_glue and self._glue_applies(x):
             return self._forward_glue(x, hw_shape, masks)
         x = x + self.attn(self.norm1(x), hw_shape, masks)
+        out = self._ffn_half(x)
+        if out is not None:
+            return out
         return self.ffn(self.norm2(x), identity=x)
 
 
