@@ -73,8 +73,9 @@ def fused_swin_glue(model, on=True):
 def fused_swin_ffn(model, on=True):
     """Sets `fused_ffn` on every `SwinBlock` of `model` and returns the blocks it switched.  With it the second half of a block --
     norm2, fc1, GELU, fc2 and the residual add -- runs as the one operator of swin_ffn.py in eval mode with nothing to
-    differentiate, wherever the operator has the shape (C = 128 or 256 with mlp_ratio 4, a GPU tensor, two biased Linear layers
-    around an exact GELU, an affine norm2) and the measurement routed that size and dtype to it (swin_ffn.ROUTED); every other
+    differentiate, wherever the operator has the shape (C = 128, 256, 512 or 1024 with mlp_ratio 4, a GPU tensor, two biased Linear
+    layers around an exact GELU, an affine norm2) and the measurement routed that size and dtype to it (swin_ffn.ROUTED,
+    swin_ffn.ROUTED_WIDE); every other
     call keeps today's path bit for bit.  It is a switch of its own and not part of fused_inference; it composes with
     fused_inference and fused_swin_glue.  Within the layer's bar of the module formulation, not bit-identical."""
     from .swin import SwinBlock

@@ -394,3 +394,6 @@ int dhdf_swin_ffn_infer(const void* x, const float* gamma, const float* beta, co
 }
 
 }  // extern "C"
+
+// the kernel family for C = 512 and 1024 and its dhdg_* entry points, on the helpers above
+#include "swin_ffn_wide.h"

@@ -326,7 +326,8 @@ class SwinBlock(nn.Module):
 
     # Opt-in (dhd_amd.fused_swin_ffn, or DHD_SWIN_FFN=1 in the environment): in eval mode with nothing to differentiate, the
     # second half of the block -- norm2, fc1, GELU, fc2 and the residual add -- runs as the one operator of swin_ffn.py
-    # (csrc/swin_ffn.hip) where it has the shape and the measurement routed it (swin_ffn.ROUTED).  Off by default: within the
+    # (csrc/swin_ffn.hip; csrc/swin_ffn_wide.h for C = 512 and 1024) where it has the shape and the measurement routed it
+    # (swin_ffn.ROUTED, swin_ffn.ROUTED_WIDE).  Off by default: within the
     # layer's bar of the module formulation, not its bits.  Composes with fused_glue and the attention's fused_infer.
     fused_ffn = bool(os.environ.get('DHD_SWIN_FFN'))
 

@@ -1,13 +1,15 @@
-"""The second half of a Swin block at inference as one HIP operator (csrc/swin_ffn.hip, include/dhd_amd_ffn.h):
+"""The second half of a Swin block at inference as one HIP operator (csrc/swin_ffn.hip, include/dhd_amd_ffn.h for C = 128 and
+256; csrc/swin_ffn_wide.h, include/dhd_amd_ffn_wide.h for C = 512 and 1024):
 
     swin_ffn_infer(x, norm_weight, norm_bias, eps, w1, b1, w2, b2) = x + fc2(gelu(fc1(layer_norm(x))))
 
-x is read once and the result written once; the normalised rows and the two (tokens x 4C) hidden tensors never exist.  Forward
+x is read once (the wide family: twice) and the result written once; the normalised rows and the two (tokens x 4C) hidden tensors never exist.  Forward
 only: nothing is saved and nothing is differentiable, which is why `SwinBlock.fused_ffn` routes to it only in eval mode with
-nothing to differentiate.  The entry points are reached through _ffn.call(name, ...) / _ffn.value(name, ...)."""
+nothing to differentiate.  The entry points are reached through _ffn.call(name, ...) / _ffn.value(name, ...), or the same two
+of _ffn_wide: the functions here dispatch on C to the family that takes it."""
 import torch
 
-from . import _ffn, _lib
+from . import _ffn, _ffn_wide, _lib
 from .trace import traced
 
 _F32, _F16, _BF16 = torch.float32, torch.float16, torch.bfloat16
@@ -26,24 +28,50 @@ ROUTED = {
     (128, _BF16, _BF16): False, (128, _F16, _F16): False, (256, _BF16, _BF16): False, (256, _F16, _F16): False,
 }
 
+# The same rule for the wide family (C = 512, 1024: DHD-L's stages 2 and 3), measured at 33 792 x 512 and 8 448 x 1024 by
+# experiments/swin_ffn_wide_bench.py -> profiles/r14/swin_ffn_wide_infer.json.  Medians in us per call, fused against the better
+# parent (largest min-max spread of the three paths); "bf16 tokens" is the residual stream in the autocast type under autocast,
+# which is what DHD-L's backbone hands these stages (PatchMerging's Linear returns the autocast type):
+#   C = 512, 33 792 rows: bf16 autocast 253 against 300 (31), fp16 autocast 259 against 304 (31), float32 533 against 1248 (88),
+#                         bf16 tokens 236 against 288 (20), fp16 tokens 246 against 287 (23)
+#   C = 1024, 8 448 rows: bf16 autocast 247 against 222 (38), fp16 autocast 247 against 228 (22), float32 734 against 1203 (76),
+#                         bf16 tokens 238 against 216 (19), fp16 tokens 241 against 220 (32)
+# At C = 1024 the half GEMMs lose (132 workgroups of 64 rows on 256 CUs): False, they stay with torch; the operator itself still
+# takes them when called directly.  A half model without autocast shares the half-token entries and was not timed on its own.
+ROUTED_WIDE = {
+    (512, _F32, _BF16): True, (512, _F32, _F16): True, (512, _F32, _F32): True,
+    (1024, _F32, _BF16): False, (1024, _F32, _F16): False, (1024, _F32, _F32): True,
+    (512, _BF16, _BF16): True, (512, _F16, _F16): True, (1024, _BF16, _BF16): False, (1024, _F16, _F16): False,
+}
+
+_WIDE = (512, 1024)
+
+
+def _family(C):
+    """(binding, entry-point stem, routing table) of the kernel family that takes C channels."""
+    if C in _WIDE:
+        return _ffn_wide, 'dhdg_swin_ffn_wide', ROUTED_WIDE
+    return _ffn, 'dhdf_swin_ffn', ROUTED
+
 
 def swin_ffn_shape_supported(x, hidden, mm_dtype=None):
     """True when the operator itself takes the tokens `x` (..., C) with `hidden` units in `mm_dtype` (default x's dtype): a GPU
-    tensor, C in {128, 256}, hidden == 4 C, and float32 tokens with any GEMM dtype or half tokens with their own."""
+    tensor, C in {128, 256, 512, 1024}, hidden == 4 C, and float32 tokens with any GEMM dtype or half tokens with their own."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.numel() > 0):
         return False
     mm_dtype = mm_dtype or x.dtype
     if x.dtype not in _lib.DTYPE_CODE or mm_dtype not in _lib.DTYPE_CODE:
         return False
-    return bool(_ffn.value('dhdf_swin_ffn_supported', x.shape[-1], int(hidden), _lib.DTYPE_CODE[x.dtype], _lib.DTYPE_CODE[mm_dtype]))
+    binding, stem, _ = _family(x.shape[-1])
+    return bool(binding.value(stem + '_supported', x.shape[-1], int(hidden), _lib.DTYPE_CODE[x.dtype], _lib.DTYPE_CODE[mm_dtype]))
 
 
 def swin_ffn_supported(x, hidden, mm_dtype=None):
     """True when a `SwinBlock` with `fused_ffn` on sends the tokens `x` (..., C) to the operator: the operator takes them
-    (swin_ffn_shape_supported) and the measurement routed that (C, dtype combination) to it (ROUTED)."""
+    (swin_ffn_shape_supported) and the measurement routed that (C, dtype combination) to it (ROUTED, ROUTED_WIDE)."""
     if not swin_ffn_shape_supported(x, hidden, mm_dtype):
         return False
-    return ROUTED.get((x.shape[-1], x.dtype, mm_dtype or x.dtype), False)
+    return _family(x.shape[-1])[2].get((x.shape[-1], x.dtype, mm_dtype or x.dtype), False)
 
 
 def _param(p, shape, name):
@@ -77,6 +105,7 @@ def swin_ffn_infer(x, norm_weight, norm_bias, eps, w1, b1, w2, b2, mm_dtype=None
         raise _lib.DhdError(f'swin_ffn_infer: no operator for tokens {tuple(x.shape)} of {x.dtype}, hidden {hidden}, GEMMs in {mm_dtype}')
     if (norm_weight is None) != (norm_bias is None):
         raise _lib.DhdError('swin_ffn_infer: norm_weight and norm_bias are given together or not at all')
+    binding, stem, _ = _family(C)
     dev = x.device
     x = _lib.dense16(x.detach())
     gamma, beta = _param(norm_weight, (C,), 'norm_weight'), _param(norm_bias, (C,), 'norm_bias')
@@ -85,9 +114,9 @@ def swin_ffn_infer(x, norm_weight, norm_bias, eps, w1, b1, w2, b2, mm_dtype=None
     xc, mc = _lib.dtype_code(x.dtype), _lib.dtype_code(mm_dtype)
     with torch.cuda.device(dev):
         out = torch.empty(x.shape, dtype=x.dtype, device=dev)
-        nbytes = _ffn.value('dhdf_swin_ffn_scratch_bytes', C, hidden, mc)
+        nbytes = binding.value(stem + '_scratch_bytes', C, hidden, mc)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _ffn.call('dhdf_swin_ffn_infer', _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2),
-                  _lib.ptr(b2), _lib.ptr(out), _lib.ptr(scratch), nbytes, xc, mc, x.numel() // C, C, hidden, float(eps),
-                  _lib.stream_ptr(dev))
+        binding.call(stem + '_infer', _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2),
+                     _lib.ptr(b2), _lib.ptr(out), _lib.ptr(scratch), nbytes, xc, mc, x.numel() // C, C, hidden, float(eps),
+                     _lib.stream_ptr(dev))
     return out
