@@ -22,6 +22,7 @@ from . import window_attn  # noqa: F401  (the module, callable as its function w
 from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
 from .swin_glue import layer_norm_rows, window_reverse_add, swin_glue_supported  # noqa: F401
 from .swin_ffn import swin_ffn_infer, swin_ffn_supported  # noqa: F401
+from .swin_seam import patch_merge_norm, patch_embed_norm, swin_seam_supported  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'
@@ -82,4 +83,19 @@ def fused_swin_ffn(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
     for m in switched:
         m.fused_ffn = bool(on)
+    return switched
+
+
+def fused_swin_seams(model, on=True):
+    """Sets `fused_seam` on every `PatchMerging` and `PatchEmbed` of `model` and returns the modules it switched.  With it the seam
+    at a stage boundary runs as an operator of swin_seam.py, in train and eval mode: patch merging's 2 x 2 gather, LayerNorm over
+    4C and cast to the dtype `reduction` reads as `patch_merge_norm` (stride 2, C a multiple of 8 up to 512, an affine norm with a
+    bias), and patch embedding's transposition of the conv output and LayerNorm as `patch_embed_norm` (C a multiple of 8 up to
+    256) -- wherever the tensor is on the GPU and the measurement routed that size and dtype to the operator
+    (swin_seam.ROUTED); every other call keeps today's path bit for bit.  It is a switch of its own: the other fused_* switches
+    do not set it and it sets none of theirs.  Within the layer's bar of torch's LayerNorm, not bit-identical."""
+    from .swin import PatchEmbed, PatchMerging
+    switched = [m for m in model.modules() if isinstance(m, (PatchEmbed, PatchMerging))]
+    for m in switched:
+        m.fused_seam = bool(on)
     return switched

@@ -350,3 +350,6 @@ extern "C" int dhdx_window_reverse_add(const void* win, const void* identity, co
     });
   });
 }
+
+// the stage seams (include/dhd_amd_seam.h): the same row form on two other row maps, in namespace dhd_seam
+#include "swin_seam.h"
