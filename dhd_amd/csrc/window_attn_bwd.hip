@@ -14,10 +14,13 @@
 // float32 the cross terms of the three bf16 products come in the other order, so its P can differ from pass A's in the last
 // bits, and dQ (pass A's P) and dK / dV (pass B's P, normalised with pass A's maximum and sum) rest on slightly different P.
 // Every element of dqkv is written by exactly one lane: no atomics, a fixed summation order, the same bytes from every call.
-// dtable: pass A adds its float32 dS (before any rounding) into an LDS copy of the head's table column with LDS float atomics;
-// the workgroup writes that column once, as one partial row of the scratch buffer, and a second launch adds the partial rows in
-// a fixed order.  No global atomics.  The order in which the LDS atomics land is not fixed, so the low bits of dtable are NOT
-// reproducible from run to run.
+// dtable: pass A adds its float32 dS (before any rounding) into an LDS copy of the head's table column with LDS float atomics,
+// one copy per wave; the workgroup adds its three copies in a fixed order and writes the column once, as one partial row of the
+// scratch buffer, and a second launch adds the partial rows in a fixed order.  No global atomics.  A copy is written by one wave
+// only, whose query tiles and atomic instructions come in program order, so the only order left open is that of the lanes of ONE
+// instruction that hit the same offset, which the LDS takes in a fixed order: dtable has been the same bytes from every call
+// wherever it was compared (tests/test_gpu_swin_composed.py: 8 tables, plain, repeated and under checkpointing).  With one copy
+// shared by the three waves the order depended on their timing and the last one or two bits changed from run to run.
 // Precisions as in the forward: float32 operands cut into two bf16 parts (three products per a * b, also for P and dS); half
 // operands one product, P and dS rounded once to the type; scores, softmax, delta and dS arithmetic in float32.
 #include "window_attn.h"
@@ -32,7 +35,7 @@ template <class T> struct LdsBwd {
   unsigned short rows[2][kParts<T>][kMaxN * kHeadDim];    // [token][channel], rows of 64 bytes.  Pass A: K, V.  Pass B: Q, dO
   unsigned short tr[2][kParts<T>][kHeadDim * kVtStride];  // [channel][token].  Pass A: K^T, -.  Pass B: Q^T, dO^T
   float table[(kMaxTable + 3) / 4 * 4];                   // the head's column of the bias table
-  float dtab[(kMaxTable + 3) / 4 * 4];                    // its gradient, over the windows of this workgroup
+  float dtab[kWaves][(kMaxTable + 3) / 4 * 4];            // its gradient, over the windows of this workgroup: one copy per wave
   float mx[kMaxN], inv[kMaxN], delta[kMaxN];              // per query: row maximum, 1 / row sum, sum_j P dP
   unsigned short kidx[kMaxKeys2];                         // y (2 Ww - 1) + x of a token
   unsigned char region[kMaxKeys2];
@@ -140,7 +143,8 @@ __global__ __launch_bounds__(kBlock) void window_attn_bwd_kernel(const T* __rest
 
   for (int i = tid; i < s.tab_len; i += kBlock) {
     lds.table[i] = table[(unsigned)i * s.nh + h];
-    lds.dtab[i] = 0.f;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v) lds.dtab[v][i] = 0.f;
   }
   for (int j = tid; j < kMaxKeys2; j += kBlock) lds.kidx[j] = j < n ? (unsigned short)((j / s.ww) * (2 * s.ww - 1) + j % s.ww) : 0;
 
@@ -233,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void window_attn_bwd_kernel(const T* __rest
                 const float x = sc[t % kMaxTiles][r] * inv * (dp[t % kMaxTiles][r] - delta);
                 ds[4 * u + r] = x;
                 const int ki = (kx[r >> 1] >> (16 * (r & 1))) & 0xffff;
-                if (qi < n && j0 + r < n) atomicAdd(&lds.dtab[qidx - ki], x);
+                if (qi < n && j0 + r < n) atomicAdd(&lds.dtab[wave][qidx - ki], x);
               }
             } else {
 #pragma unroll
@@ -304,7 +308,8 @@ __global__ __launch_bounds__(kBlock) void window_attn_bwd_kernel(const T* __rest
 
   __syncthreads();
   float* row = partial + ((unsigned)chunk * s.nh + h) * (unsigned)s.tab_len;
-  for (int i = tid; i < s.tab_len; i += kBlock) row[i] = lds.dtab[i];
+  static_assert(kWaves == 3, "the sum of the per-wave copies below is written out for three waves");
+  for (int i = tid; i < s.tab_len; i += kBlock) row[i] = (lds.dtab[0][i] + lds.dtab[1][i]) + lds.dtab[2][i];
 }
 
 // dtable[r, h] = the partial rows of head h added in the order of the chunks

@@ -124,9 +124,9 @@ def window_attn(qkv, table, window_size, num_heads, scale, regions=None, gemm=No
     """window_attn_infer with a backward: the same arguments and the same result, differentiable in `qkv` and `table`.  The
     forward is the inference operator and saves qkv, table and regions and nothing else; the backward is one call of
     dhd_window_attn_backward, which recomputes the softmax and returns dqkv in qkv's dtype and layout (what the qkv Linear's
-    backward consumes, no permute back) and dtable in the table's dtype and shape.  dqkv is reproducible bit for bit; the low
-    bits of dtable are not (LDS float atomics).  Works under torch.autocast (half qkv, float32 table) and under
-    checkpoint(..., use_reentrant=False).  The backward allocates dqkv, dtable and its scratch from the caching allocator."""
+    backward consumes, no permute back) and dtable in the table's dtype and shape.  dqkv is reproducible bit for bit, and so
+    is dtable as far as tested (LDS float atomics into one copy per wave, see csrc/window_attn_bwd.hip).  Works under
+    torch.autocast (half qkv, float32 table) and under checkpoint(..., use_reentrant=False).  The backward allocates dqkv, dtable and its scratch from the caching allocator."""
     return _WindowAttn.apply(qkv, table, regions, tuple(window_size), num_heads, scale, gemm)
 
 

@@ -880,8 +880,10 @@ int dhd_window_attn_infer(const void* qkv, int dtype, const float* table, const 
  *     half: one product, P and dS rounded once to qkv's type, dq / dk / dv rounded once at the end; softmax, delta and dS in
  *     float32).  dtable is accumulated and stored in float32 from the unrounded dS in every precision.
  *     Reproducibility: dqkv is written without atomics in a fixed summation order -- two calls on the same inputs give the same
- *     bytes.  dtable is accumulated per workgroup with LDS float atomics (no global atomics; the per-workgroup partial rows in
- *     `scratch` are then added in a fixed order by a second launch), so its low bits are NOT reproducible from run to run.
+ *     bytes.  dtable is accumulated per workgroup with LDS float atomics, each wave into a copy of its own that no other wave
+ *     touches (no global atomics; the copies, and then the per-workgroup partial rows in `scratch`, are added in a fixed
+ *     order): the same bytes from call to call on this hardware as far as tested, which rests on the LDS taking the lanes of
+ *     one atomic instruction that hit one address in a fixed order, not on a documented guarantee.
  *     dq on the one hand and dk / dv on the other are built from two evaluations of P: the scores are computed once as K Q^T and
  *     once as Q K^T, and in float32 (three bf16 products, the cross terms in the other order) exp(S - max) can differ in its
  *     last bits between the two, so sum_j P_ij of the second evaluation is 1 only to float32 rounding.  Inside the 1e-4 bar.

@@ -7,8 +7,8 @@ Inputs, reference gradients and bounds: window_attn_train_inputs.py.  |g - G| <=
   dqkv in fp16 / bf16      E = 2 E0, E0 = max |G - chain| computed on the CPU (P and dS rounded to the half type where the products
                            consume them, dQ / dK / dV rounded at the end); the factor 2 covers summation order and where exactly
                            the kernel rounds.
-dqkv is reproducible bit for bit; dtable is accumulated with LDS float atomics and the header says its low bits are not, so
-dtable is compared within its bound and never byte for byte.
+dqkv is reproducible bit for bit; dtable is accumulated with LDS float atomics and the header gives no guarantee for its low
+bits, so here dtable is compared within its bound and never byte for byte (tests/test_gpu_swin_composed.py compares its bytes).
 Measured errors are printed by test_against_the_float64_gradients; docs/LAB_NOTEBOOK.md (R11.1) is where they are recorded."""
 import copy
 
