@@ -12,6 +12,12 @@
 //   bin_bce_partial     one thread per pixel over the C channel planes (coalesced across pixels)
 //   bin_bce_finalize    loss = weight * sum / max(1, n_fg)   (double)
 //   bin_bce_grad        torch's binary_cross_entropy backward, (p - y) / max((1 - p) p, 1e-12)
+//
+// NaN: a NaN probability at a foreground pixel makes the loss NaN (the -100 clamp of the logarithms is a select that keeps it)
+// and the gradient NaN at that element only (the numerator carries it; the 1e-12 floor of the denominator does not hide it).
+// Background pixels are never read: whatever they hold, the loss is unchanged and their gradients are 0.  No foreground
+// pixel: loss 0, gradient 0.  Labels: an empty window (all zeros) and a minimum below the first bin or at / beyond bin
+// n_bins + 1 (1e5 included) get bin 0, "no label".
 #include "common.h"
 
 namespace {
@@ -79,8 +85,9 @@ __global__ __launch_bounds__(kBlock) void bin_bce_partial(const float* __restric
     const float* p = pred + (size_t)(pix / hw) * c * hw + (pix % hw);
     for (int k = 0; k < c; ++k) {
       const float v = p[(size_t)k * hw];
-      // F.binary_cross_entropy clamps both logs at -100
-      s -= k == label ? fmaxf(logf(v), -100.f) : fmaxf(log1pf(-v), -100.f);
+      // F.binary_cross_entropy clamps both logs at -100; a select, so that a NaN probability stays NaN (fmaxf would return -100)
+      const float l = k == label ? logf(v) : log1pf(-v);
+      s -= l < -100.f ? -100.f : l;
     }
   }
   s = wave_sum_bcast(s);

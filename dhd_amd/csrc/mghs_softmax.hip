@@ -16,6 +16,10 @@
 // torch's do (asserted bit for bit against torch on the GPU, tests/test_gpu_parity.py) and the band id is the argmax of
 // exactly the probabilities the caller gets back (first maximum wins, as torch.argmax on CPU / the reference).
 //
+// Saturated rows follow torch as well: a bin at -inf gets probability 0, bins at the type's largest finite value share 1 between
+// them, and the rows torch defines as NaN (+inf with anything: inf - inf; every bin -inf: 0 / 0) are NaN here.  The band of a
+// NaN row is unspecified (no comparison with NaN holds, so it is bin 0's).
+//
 // Backward: gx = (g - sum_k g_k y_k) * y per pixel (float32, in bin order), written together with the context gradient into
 // ONE (BN, CT, fH, fW) tensor of x_d's dtype and layout; channels past D + C get zeros.
 #include "lift_device.h"

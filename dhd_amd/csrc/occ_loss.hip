@@ -14,6 +14,11 @@
 //   pass 2 (occ_loss_grad)  re-reads the logits, recomputes the softmax and writes
 //                           dL/dz_k = valid p_k (a_k + b_k [t=k] - sum_j p_j a_j - p_t b_t) + ce (p_k - [t=k]),
 //                           a_i = dL/dP_i, b_i = dL/dN_i evaluated per block from the stored totals.
+// Edges.  No valid voxel (an empty camera mask, every label ignored): cross entropy and sem scal are 0 / 0 = NaN and geo scal is
+// 3 x -log(1e-5), as the reference's formulas give; every gradient is 0.  `P_i > 0` (whether class i's precision term exists) is
+// decided on the float32 sums, as in the reference: a class whose probability underflows in every valid voxel has none.  A
+// logit of -inf is a probability of 0.  NaN: a NaN logit in a valid voxel makes all three losses NaN; an excluded voxel's
+// logits are never read (the reference multiplies its cross entropy by 0 and would return NaN there).
 // Traffic: 2 x 72 B read + 72 B written per voxel (+2 B labels/mask each pass); no (M,18) temporaries.
 // Logit tiles go through LDS so that global accesses are 16-byte coalesced although a voxel's 18 logits
 // are 72 contiguous bytes: a thread reads its voxel as nine conflict-free ds_read_b64.
@@ -130,20 +135,24 @@ __global__ __launch_bounds__(kBlock) void occ_loss_sums(const float* __restrict_
   }
 }
 
-__device__ __forceinline__ double nll_clamped(double x) {
-  // binary_cross_entropy_with_logits(inverse_sigmoid(x), 1): inverse_sigmoid (semkitti_loss.py:8-16) takes the
-  // float32 value into [1e-5, 1-1e-5) in steps of 1e-5 (one step for x in [0,1]); the result is -log(x')
-  x = (double)(float)x;
-  if (x >= 1.0 - 1e-5) x -= 1e-5;
-  if (x < 1e-5) x += 1e-5;
-  return -log(x);
+// inverse_sigmoid (semkitti_loss.py:8-16) moves the float32 value of x into [1e-5, 1-1e-5) by two `while` loops that step by
+// 1e-5.  Which steps are taken is decided as the reference decides it, on float32 values against float32 thresholds: one step
+// for x in [1-1e-5, 1) -- and TWO for x == 1.0f (a class every voxel of which is predicted with p = 1: 1.0f - 1e-5 rounds to
+// float32(1 - 1e-5) itself, which is not below it) -- one step up for x < 1e-5.  The steps themselves are taken in double.  The
+// loops are bounded (two steps down, one up: all that a ratio in [0, 1] can take); a NaN takes none and passes through.
+__device__ __forceinline__ double inverse_sigmoid_arg(double ratio) {
+  double x = (double)(float)ratio;
+  for (int i = 0; i < 2 && (float)x >= 0.99999f; ++i) x -= 1e-5;
+  if ((float)x < 1e-5f) x += 1e-5;
+  return x;
 }
+
+// binary_cross_entropy_with_logits(inverse_sigmoid(x), 1) = -log(x')
+__device__ __forceinline__ double nll_clamped(double x) { return -log(inverse_sigmoid_arg(x)); }
 
 // derivative of nll_clamped(num/den) with respect to num and den
 __device__ __forceinline__ void d_nll(double num, double den, double* d_num, double* d_den) {
-  double x = (double)(float)(num / den);
-  if (x >= 1.0 - 1e-5) x -= 1e-5;
-  if (x < 1e-5) x += 1e-5;
+  const double x = inverse_sigmoid_arg(num / den);
   *d_num = -1.0 / (x * den);
   *d_den = num / (x * den * den);
 }
@@ -372,7 +381,8 @@ int dhd_occ_loss_backward(const float* logits, const uint8_t* labels, const uint
 // Metric_mIoU.hist_info (core/evaluation/occ_metrics.py:79-104: 18x18 confusion counts over the
 // camera-visible voxels with a label in [0, 18)), in one pass over the (M,18) logits.
 // argmax of the logits = argmax of their softmax (first maximum wins); the two can differ only where
-// the two largest probabilities round to the same float.
+// the two largest probabilities round to the same float.  Equal logits, +0 against -0 and a row of -inf give class 0 (the
+// comparison is a strict >); which class a row with a NaN at k != 0 gets is unspecified.
 // ------------------------------------------------------------------------------------------------
 namespace {
 

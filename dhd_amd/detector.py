@@ -410,9 +410,11 @@ NUSC_CLASS_FREQUENCIES = np.array([944004, 1897170, 152386, 2391677, 16957802, 7
 
 def _neg_log_clamped(x):
     """binary_cross_entropy_with_logits(inverse_sigmoid(x), 1) == -log(x'), where inverse_sigmoid's two
-    while-loops (semkitti_loss.py:8-16) move x into [1e-5, 1-1e-5) in one step for x in [0, 1]."""
+    while-loops (semkitti_loss.py:8-16) move the float32 x into [1e-5, 1-1e-5) in steps of 1e-5: one step for
+    x in [0, 1), two for x == 1.0 (1.0 - 1e-5 is float32(1 - 1e-5) itself, which is not below it)."""
     x = x.float()
-    x = torch.where(x >= 1 - 1e-5, x - 1e-5, x)
+    for _ in range(2):
+        x = torch.where(x >= 1 - 1e-5, x - 1e-5, x)
     x = torch.where(x < 1e-5, x + 1e-5, x)
     return -torch.log(x)
 
