@@ -21,7 +21,8 @@ from .deform_conv import deform_conv_infer, deform_conv_infer_supported  # noqa:
 from . import window_attn  # noqa: F401  (the module, callable as its function window_attn)
 from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
 from .swin_glue import layer_norm_rows, window_reverse_add, swin_glue_supported  # noqa: F401
-from .swin_ffn import swin_ffn_infer, swin_ffn_supported  # noqa: F401
+from . import swin_ffn  # noqa: F401  (the module, callable as its function swin_ffn)
+from .swin_ffn import swin_ffn_infer, swin_ffn_supported, swin_ffn_train_supported  # noqa: F401
 from .swin_seam import patch_merge_norm, patch_embed_norm, swin_seam_supported  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
@@ -83,6 +84,21 @@ def fused_swin_ffn(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
     for m in switched:
         m.fused_ffn = bool(on)
+    return switched
+
+
+def fused_swin_ffn_training(model, on=True):
+    """Sets `fused_ffn_train` on every `SwinBlock` of `model` and returns the blocks it switched.  With it the second half of a
+    block -- norm2, fc1, GELU, fc2, DropPath and the residual add -- runs as `swin_ffn`, the fused forward and its recompute HIP
+    backward, in train and eval mode, with or without grad, wherever the operator has the shape (C = 128 or 256 with mlp_ratio 4,
+    a GPU tensor, two biased Linear layers around an exact GELU, an affine norm2), the FFN's dropout is inactive and the
+    measurement routed that size and dtype to it (swin_ffn.ROUTED_TRAIN); every other call keeps today's path bit for bit.  The
+    random stream of an active DropPath is unchanged.  It is a switch of its own: the other fused_* switches do not set it and
+    it sets none of theirs.  Within the layer's bar of the module formulation, not bit-identical."""
+    from .swin import SwinBlock
+    switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
+    for m in switched:
+        m.fused_ffn_train = bool(on)
     return switched
 
 

@@ -165,10 +165,17 @@ __device__ __forceinline__ float sum8(const float* s) { return ((s[0] + s[1]) + 
 
 // KEEP: the row's own bytes stay in registers from the first load to the residual add; otherwise the epilogue loads them again
 // (the one combination whose registers do not hold them: C = 256 with the two-part float32 operands).
-template <class X, class M, int C, bool KEEP>
+// S: what multiplies the branch before the residual add.  NoScale (inference: nothing, and nothing is compiled for it) or the
+// per-image factor of the training forward (swin_ffn_train.h).
+struct NoScale {
+  static constexpr bool kOn = false;
+};
+
+template <class X, class M, int C, bool KEEP, class S>
 __global__ __launch_bounds__(kBlock) void swin_ffn_kernel(const X* __restrict__ x, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, const u32x4* __restrict__ stream,
-                                                          const float* __restrict__ b2, X* __restrict__ out, long rows, float eps) {
+                                                          const float* __restrict__ b2, X* __restrict__ out, long rows, float eps,
+                                                          S scale) {
   using G = Geo<M, C>;
   constexpr int P = G::P, N = G::N, R = G::R, KS = G::KS, NT = G::NT, HT = G::HT, RW = kRawVecs<X>;
   static_assert(N % R == 0, "the ring position of a fragment must not depend on the hidden tile");
@@ -177,6 +184,8 @@ __global__ __launch_bounds__(kBlock) void swin_ffn_kernel(const X* __restrict__ 
   if (p0 >= rows) return;
   const bool live = p0 + r < rows;   // a lane past the last row computes on the last row and stores nothing
   const long p = live ? p0 + r : rows - 1;
+  float f = 1.f;
+  if constexpr (S::kOn) f = scale.factor[p / scale.rows_per_image];   // the row's image; applied in float32 in the epilogue
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(stream), 0, (unsigned)G::kScratchBytes, 0x00020000);
   // the ring: fragment i of tile t sits in ring[i % R]; its slot is refilled with fragment i + R as soon as it is consumed
   // (the refills of the last fragments read the padding behind the stream, see kScratchBytes)
@@ -318,8 +327,13 @@ __global__ __launch_bounds__(kBlock) void swin_ffn_kernel(const X* __restrict__ 
       }
       const f32x4* bp = reinterpret_cast<const f32x4*>(b2 + 16 * ks + 8 * h);
       const f32x4 c0 = bp[0], c1 = bp[1];
+      if constexpr (S::kOn) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = xv[j] + (acc[n][8 * s + j] + (j < 4 ? c0[j & 3] : c1[j & 3]));
+        for (int j = 0; j < 8; ++j) o[j] = xv[j] + f * (acc[n][8 * s + j] + (j < 4 ? c0[j & 3] : c1[j & 3]));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = xv[j] + (acc[n][8 * s + j] + (j < 4 ? c0[j & 3] : c1[j & 3]));
+      }
       if (live) {
         raw16<X>* q = reinterpret_cast<raw16<X>*>(orow + 16 * ks);
 #pragma unroll
@@ -342,17 +356,17 @@ size_t scratch_bytes(int c, int mm_dtype) {
   return mm_dtype == DHD_F32 ? Geo<float, 256>::kScratchBytes : Geo<__bf16, 256>::kScratchBytes;
 }
 
-template <class X, class M, int C>
+template <class X, class M, int C, class S = NoScale>
 int launch(const void* x, const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2, const float* b2,
-           void* out, void* scratch, long rows, float eps, hipStream_t st) {
+           void* out, void* scratch, long rows, float eps, hipStream_t st, S scale = S{}) {
   using G = Geo<M, C>;
   constexpr bool keep = !(C == 256 && std::is_same_v<M, float>);
   u32x4* stream = static_cast<u32x4*>(scratch);
   constexpr int n_pack = G::HT * G::N * 64;
   hipLaunchKernelGGL((pack_stream_kernel<M, C>), dim3(dhd_cdiv(n_pack, kPackBlock)), dim3(kPackBlock), 0, st, w1, b1, w2, stream);
   DHD_LAUNCH_CHECK();
-  hipLaunchKernelGGL((swin_ffn_kernel<X, M, C, keep>), dim3(dhd_cdiv(rows, kRowsPerBlock)), dim3(kBlock), 0, st,
-                     static_cast<const X*>(x), gamma, beta, stream, b2, static_cast<X*>(out), rows, eps);
+  hipLaunchKernelGGL((swin_ffn_kernel<X, M, C, keep, S>), dim3(dhd_cdiv(rows, kRowsPerBlock)), dim3(kBlock), 0, st,
+                     static_cast<const X*>(x), gamma, beta, stream, b2, static_cast<X*>(out), rows, eps, scale);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -397,3 +411,6 @@ int dhdf_swin_ffn_infer(const void* x, const float* gamma, const float* beta, co
 
 // the kernel family for C = 512 and 1024 and its dhdg_* entry points, on the helpers above
 #include "swin_ffn_wide.h"
+
+// the training pair for C = 128 and 256 (forward with a per-image factor, recompute backward) and its dhdt_* entry points
+#include "swin_ffn_train.h"

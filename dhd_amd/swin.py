@@ -380,27 +380,60 @@ class SwinBlock(nn.Module):
             return False
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in (*self.norm2.parameters(), *self.ffn.parameters()))):
             return False
-        # the reference structure: two Linear layers with biases, exact GELU, an affine norm2 over C (dropout is inactive in eval)
+        if not self._ffn_structure(x):
+            return False
+        from .swin_ffn import swin_ffn_supported
+        return swin_ffn_supported(x, self.ffn.layers[0][0].out_features, torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
+
+    def _ffn_structure(self, x):
+        """True when norm2 + ffn have the reference structure over the C channels of x: two Linear layers with biases, exact GELU,
+        an affine norm2 (the two dropouts are not looked at: inactive in eval)."""
         n, L = self.norm2, self.ffn.layers
         C = x.shape[-1]
         if not (isinstance(n, nn.LayerNorm) and n.elementwise_affine and n.bias is not None and tuple(n.normalized_shape) == (C,)):
             return False
-        if not (len(L) == 3 and isinstance(L[0], nn.Sequential) and len(L[0]) == 3 and isinstance(L[0][0], nn.Linear)
+        return (len(L) == 3 and isinstance(L[0], nn.Sequential) and len(L[0]) == 3 and isinstance(L[0][0], nn.Linear)
                 and isinstance(L[0][1], nn.GELU) and L[0][1].approximate == 'none' and isinstance(L[1], nn.Linear)
                 and L[0][0].bias is not None and L[1].bias is not None and L[0][0].in_features == C and L[1].out_features == C
-                and L[1].in_features == L[0][0].out_features):
+                and L[1].in_features == L[0][0].out_features)
+
+    # Opt-in (dhd_amd.fused_swin_ffn_training, or DHD_SWIN_FFN_TRAIN=1 in the environment so that a whole training step can be
+    # A/B'd): the second half of the block with its DropPath runs as swin_ffn.swin_ffn -- the fused forward, which saves the
+    # tokens and no hidden tensor, and its recompute HIP backward (csrc/swin_ffn_train.h) -- in train and eval mode, with or
+    # without grad, where it has the shape, the FFN's dropout is inactive and the measurement routed it (swin_ffn.ROUTED_TRAIN).
+    # A switch of its own; off by default: within the layer's bar of the module formulation, not its bits.
+    fused_ffn_train = bool(os.environ.get('DHD_SWIN_FFN_TRAIN'))
+
+    def _ffn_train_applies(self, x):
+        """True when the block's second half runs as swin_ffn on the tokens x (B, ..., C); otherwise today's path runs."""
+        if not (self.fused_ffn_train and torch.is_tensor(x) and x.is_cuda and x.dim() >= 2 and self._ffn_structure(x)):
             return False
-        from .swin_ffn import swin_ffn_supported
-        return swin_ffn_supported(x, L[0][0].out_features, torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
+        L, dp = self.ffn.layers, self.ffn.dropout_layer
+        if not (isinstance(dp, DropPath) and all(isinstance(d, nn.Dropout) and not (d.training and d.p > 0) for d in (L[0][2], L[2]))):
+            return False
+        from .swin_ffn import swin_ffn_train_supported
+        return swin_ffn_train_supported(x, L[0][0].out_features, torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
 
     def _ffn_half(self, x):
-        """x + ffn(norm2(x)): the fused operator where _ffn_applies, else None."""
-        if not (self.fused_ffn and self._ffn_applies(x)):
+        """x + ffn(norm2(x)): a fused operator where _ffn_applies (inference, which keeps precedence) or _ffn_train_applies, else
+        None."""
+        infer = self.fused_ffn and self._ffn_applies(x)
+        if not (infer or (self.fused_ffn_train and self._ffn_train_applies(x))):
             return None
-        from .swin_ffn import swin_ffn_infer
         fc1, fc2 = self.ffn.layers[0][0], self.ffn.layers[1]
-        return swin_ffn_infer(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
-                              torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
+        cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype      # what fc1 casts its input to
+        if infer:
+            from .swin_ffn import swin_ffn_infer
+            return swin_ffn_infer(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias, cdt)
+        from .swin_ffn import swin_ffn
+        dp, scale = self.ffn.dropout_layer, None
+        if dp.training and dp.drop_prob != 0.:
+            # DropPath.forward's draw, call for call and in the dtype of layers(x) (the RNG stream does not change), as the
+            # per-image factor of the branch
+            keep = 1 - dp.drop_prob
+            kept = keep + torch.rand((x.shape[0],) + (1,) * (x.dim() - 1), dtype=cdt, device=x.device)
+            scale = kept.floor().float().div(keep).view(-1)
+        return swin_ffn(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias, cdt, scale)
 
     def _glue_applies(self, x):
         """True when forward takes the fused route for the tokens x (B, L, C)."""
