@@ -53,8 +53,10 @@ EXPECTED_ALL_ON = (
     ('stage3', [LN, ATTN, ADD, WIDE, LN, ATTN, ADD, WIDE]),                  # 3 x 5 of 1024: 1 window
 )
 # The gradient run (fused_training, glue and seams; eval mode with grad): the forward per block is norm1 into the windows, the
-# attention and reverse + add (norm2 and the FFN are torch's: the map is small and float32, and the FFN operator is forward
-# only); the backward per block is the window partition of the gradient (reverse + add), the attention's and norm1's.
+# attention and reverse + add (norm2 and the FFN are torch's: the map is small and float32, fused_swin_ffn's operator is for
+# inference, and the training operator's switch, fused_swin_ffn_training, is not set here: tests/test_gpu_swin_ffn_train.py and
+# tests/test_gpu_swin_train_step.py set it); the backward per block is the window partition of the gradient (reverse + add),
+# the attention's and norm1's.
 EXPECTED_GRAD_FORWARD = tuple((label, [n for n in names if n not in (NARROW, WIDE)]) for label, names in EXPECTED_ALL_ON)
 EXPECTED_GRAD_BACKWARD = {'embed': [EMBED_B], 'merge': [MERGE_B], 'stage': [ROWS, ATTN_B, LN_B, ROWS, ATTN_B, LN_B]}
 
@@ -384,8 +386,10 @@ def _grad_errors(grads, xg):
 
 
 def test_gradients_float32(gpu, monkeypatch):
-    """Eval mode with grad (DropPath is the identity and the fixture applies): fused_training, the glue and the seams on; the FFN
-    operator records no call."""
+    """Eval mode with grad (DropPath is the identity and the fixture applies): fused_training, the glue and the seams on.  No FFN
+    operator records a call: the inference one does not run where something is differentiated, and the training one
+    (fused_swin_ffn_training) is left off here; test_composed_backbone_gradients of tests/test_gpu_swin_ffn_train.py is this test
+    with it on, and tests/test_gpu_swin_train_step.py holds the train-mode step with every switch on."""
     _route_all(monkeypatch)
     g, x = _g(), _x(gpu)
     forward, backward, per_stage = _grad_tables()
@@ -466,19 +470,23 @@ def test_with_cp_is_bit_identical(gpu, monkeypatch):
 # ------------------------------------------------------------------------------------------------ 6. train mode draws
 
 def test_train_mode_draws(gpu, monkeypatch):
-    """net.train() with drop_path_rate 0.1: no fixture.  Two runs from one seed give the same bits, and the switched-off model
-    leaves the generator where the switched-on one does: DropPath's draws are the same in number."""
+    """net.train() with drop_path_rate 0.1, with fused_training, the glue, the seams and fused_swin_ffn_training on.  Two runs from
+    one seed give the same bits, and the switched-off model leaves the generator where the switched-on one does: DropPath's
+    draws are the same in number.  That the result is right is held by tests/test_gpu_swin_train_step.py."""
+    import dhd_amd
     _route_all(monkeypatch)
     x = _x(gpu)
     states, runs = {}, []
     seen = _recorder(monkeypatch)
     for on in (True, True, False):
         net = _switch(_net(gpu), glue=on, seams=on, train=on).train()
+        assert len(dhd_amd.fused_swin_ffn_training(net, on)) == 8
         torch.cuda.manual_seed(1234)
         del seen[:]
         outs, xg, _ = _grad_step(net, x)
         states.setdefault(on, []).append(torch.cuda.get_rng_state(gpu))
-        assert (ATTN_B in seen and LN_B in seen and MERGE_B in seen) == on, seen
+        assert (ATTN_B in seen and LN_B in seen and MERGE_B in seen and 'dhdt_swin_ffn_backward' in seen) == on, seen
+        assert any(n.startswith(('dhd_window_attn', 'dhdx_', 'dhds_', 'dhdt_')) for n in seen) == on, seen
         if on:
             runs.append(outs + [xg])
     assert all(torch.equal(a, b) for a, b in zip(*runs))
