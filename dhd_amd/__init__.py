@@ -22,7 +22,7 @@ from . import window_attn  # noqa: F401  (the module, callable as its function w
 from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
 from .swin_glue import layer_norm_rows, window_reverse_add, swin_glue_supported  # noqa: F401
 from . import swin_ffn  # noqa: F401  (the module, callable as its function swin_ffn)
-from .swin_ffn import swin_ffn_infer, swin_ffn_supported, swin_ffn_train_supported  # noqa: F401
+from .swin_ffn import swin_ffn_infer, swin_ffn_supported, swin_ffn_train_supported, swin_ffn_train_wide_supported  # noqa: F401
 from .swin_seam import patch_merge_norm, patch_embed_norm, swin_seam_supported  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
@@ -99,6 +99,20 @@ def fused_swin_ffn_training(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
     for m in switched:
         m.fused_ffn_train = bool(on)
+    return switched
+
+
+def fused_swin_ffn_training_wide(model, on=True):
+    """Sets `fused_ffn_train_wide` on every `SwinBlock` of `model` and returns the blocks it switched: fused_swin_ffn_training's
+    route at C = 512 (DHD-L's stage 2) through the wide training family -- the wide forward with DropPath's factor and its
+    recompute HIP backward -- under the same conditions, wherever the measurement routed that dtype combination to it
+    (swin_ffn.ROUTED_TRAIN_WIDE); every other call keeps today's path bit for bit.  The random stream of an active DropPath is
+    unchanged.  It is a switch of its own: fused_swin_ffn_training does not set it and it does not set that one, so a model with
+    only the other switches on makes the calls it made before.  C = 1024 has no training operator."""
+    from .swin import SwinBlock
+    switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
+    for m in switched:
+        m.fused_ffn_train_wide = bool(on)
     return switched
 
 

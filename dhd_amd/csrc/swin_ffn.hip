@@ -414,3 +414,6 @@ int dhdf_swin_ffn_infer(const void* x, const float* gamma, const float* beta, co
 
 // the training pair for C = 128 and 256 (forward with a per-image factor, recompute backward) and its dhdt_* entry points
 #include "swin_ffn_train.h"
+
+// the training pair for C = 512 in the wide family's form and its dhdu_* entry points, on both of the above
+#include "swin_ffn_wide_train.h"

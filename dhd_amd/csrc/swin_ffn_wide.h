@@ -126,11 +126,13 @@ template <class M> __device__ __forceinline__ f32x16 mfma_parts(const u32x4 (&w)
   return mfma16<M>(w[0], b[0], c);
 }
 
-template <class X, class M, int C>
+// S: what multiplies the branch before the residual add, as in swin_ffn_kernel: NoScale (inference: nothing, and nothing is
+// compiled for it) or the per-image factor of the training forward (swin_ffn_wide_train.h).
+template <class X, class M, int C, class S = NoScale>
 __global__ __launch_bounds__(kWideBlock) void swin_ffn_wide_kernel(const X* __restrict__ x, const float* __restrict__ gamma,
                                                                    const float* __restrict__ beta, const u32x4* __restrict__ stream,
                                                                    const float* __restrict__ b2, X* __restrict__ out, long rows,
-                                                                   float eps) {
+                                                                   float eps, S scale) {
   using G = WGeo<M, C>;
   constexpr int P = G::P, T = G::T, N = G::N, R = G::R, KS = G::KS, HS = G::HS, UTW = G::UTW, RT = G::RT, MT = G::MT, RW = kRawVecs<X>;
   constexpr int NV = C / 512;   // 8-channel vectors of a row per lane in the LayerNorm pass
@@ -317,6 +319,8 @@ __global__ __launch_bounds__(kWideBlock) void swin_ffn_wide_kernel(const X* __re
     const long p = live ? p0 + 32 * rt + r : rows - 1;
     const X* xrow = x + (size_t)p * C + 8 * h;
     X* orow = out + (size_t)p * C + 8 * h;
+    float f = 1.f;
+    if constexpr (S::kOn) f = scale.factor[p / scale.rows_per_image];   // the row's image; applied in float32
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -328,8 +332,13 @@ __global__ __launch_bounds__(kWideBlock) void swin_ffn_wide_kernel(const X* __re
         widen8<X>(raw, xv);
         const f32x4* bp = reinterpret_cast<const f32x4*>(b2 + 16 * ks + 8 * h);
         const f32x4 c0 = bp[0], c1 = bp[1];
+        if constexpr (S::kOn) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = xv[j] + (acc[m][rt][8 * s + j] + (j < 4 ? c0[j & 3] : c1[j & 3]));
+          for (int j = 0; j < 8; ++j) o[j] = xv[j] + f * (acc[m][rt][8 * s + j] + (j < 4 ? c0[j & 3] : c1[j & 3]));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = xv[j] + (acc[m][rt][8 * s + j] + (j < 4 ? c0[j & 3] : c1[j & 3]));
+        }
         if (live) {
           raw16<X>* q = reinterpret_cast<raw16<X>*>(orow + 16 * ks);
 #pragma unroll
@@ -346,16 +355,16 @@ size_t wide_scratch_bytes(int c, int mm_dtype) {
   return mm_dtype == DHD_F32 ? WGeo<float, 1024>::kScratchBytes : WGeo<__bf16, 1024>::kScratchBytes;
 }
 
-template <class X, class M, int C>
+template <class X, class M, int C, class S = NoScale>
 int wide_launch(const void* x, const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2,
-                const float* b2, void* out, void* scratch, long rows, float eps, hipStream_t st) {
+                const float* b2, void* out, void* scratch, long rows, float eps, hipStream_t st, S scale = S{}) {
   using G = WGeo<M, C>;
   u32x4* stream = static_cast<u32x4*>(scratch);
   constexpr int n_pack = kWideWaves * G::NCH * G::N * 64;
   hipLaunchKernelGGL((pack_wide_kernel<M, C>), dim3(dhd_cdiv(n_pack, kPackBlock)), dim3(kPackBlock), 0, st, w1, b1, w2, stream);
   DHD_LAUNCH_CHECK();
-  hipLaunchKernelGGL((swin_ffn_wide_kernel<X, M, C>), dim3(dhd_cdiv(rows, (long)G::T)), dim3(kWideBlock), 0, st,
-                     static_cast<const X*>(x), gamma, beta, stream, b2, static_cast<X*>(out), rows, eps);
+  hipLaunchKernelGGL((swin_ffn_wide_kernel<X, M, C, S>), dim3(dhd_cdiv(rows, (long)G::T)), dim3(kWideBlock), 0, st,
+                     static_cast<const X*>(x), gamma, beta, stream, b2, static_cast<X*>(out), rows, eps, scale);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }

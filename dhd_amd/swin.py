@@ -414,11 +414,29 @@ class SwinBlock(nn.Module):
         from .swin_ffn import swin_ffn_train_supported
         return swin_ffn_train_supported(x, L[0][0].out_features, torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
 
+    # Opt-in (dhd_amd.fused_swin_ffn_training_wide, or DHD_SWIN_FFN_TRAIN_WIDE=1 in the environment): the same route at C = 512
+    # (DHD-L's stage 2), through the wide training family (csrc/swin_ffn_wide_train.h) where the measurement routed it
+    # (swin_ffn.ROUTED_TRAIN_WIDE).  A switch of its own, so that fused_ffn_train alone keeps every call it makes today; off by
+    # default.
+    fused_ffn_train_wide = bool(os.environ.get('DHD_SWIN_FFN_TRAIN_WIDE'))
+
+    def _ffn_train_wide_applies(self, x):
+        """True when the block's second half runs as swin_ffn's wide family on the tokens x (B, ..., 512): _ffn_train_applies'
+        conditions with the wide family's predicate."""
+        if not (self.fused_ffn_train_wide and torch.is_tensor(x) and x.is_cuda and x.dim() >= 2 and self._ffn_structure(x)):
+            return False
+        L, dp = self.ffn.layers, self.ffn.dropout_layer
+        if not (isinstance(dp, DropPath) and all(isinstance(d, nn.Dropout) and not (d.training and d.p > 0) for d in (L[0][2], L[2]))):
+            return False
+        from .swin_ffn import swin_ffn_train_wide_supported
+        return swin_ffn_train_wide_supported(x, L[0][0].out_features, torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype)
+
     def _ffn_half(self, x):
-        """x + ffn(norm2(x)): a fused operator where _ffn_applies (inference, which keeps precedence) or _ffn_train_applies, else
-        None."""
+        """x + ffn(norm2(x)): a fused operator where _ffn_applies (inference, which keeps precedence), _ffn_train_applies or
+        _ffn_train_wide_applies, else None."""
         infer = self.fused_ffn and self._ffn_applies(x)
-        if not (infer or (self.fused_ffn_train and self._ffn_train_applies(x))):
+        if not (infer or (self.fused_ffn_train and self._ffn_train_applies(x))
+                or (self.fused_ffn_train_wide and self._ffn_train_wide_applies(x))):
             return None
         fc1, fc2 = self.ffn.layers[0][0], self.ffn.layers[1]
         cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else x.dtype      # what fc1 casts its input to

@@ -8,15 +8,16 @@ only: nothing is saved and nothing is differentiable, which is why `SwinBlock.fu
 nothing to differentiate.  The entry points are reached through _ffn.call(name, ...) / _ffn.value(name, ...), or the same two
 of _ffn_wide: the functions here dispatch on C to the family that takes it.
 
-In training the same half, with its DropPath, is `swin_ffn` (csrc/swin_ffn_train.h, include/dhd_amd_ffn_train.h; C = 128 and 256):
-an autograd function whose forward saves the tokens and nothing of the hidden tensors and whose backward recomputes them in one
-HIP call, `SwinBlock.fused_ffn_train`'s route."""
+In training the same half, with its DropPath, is `swin_ffn` (csrc/swin_ffn_train.h, include/dhd_amd_ffn_train.h for C = 128 and
+256; csrc/swin_ffn_wide_train.h, dhd_amd/include/dhd_amd_ffn_wide_train.h for C = 512): an autograd function whose forward saves
+the tokens and nothing of the hidden tensors and whose backward recomputes them in one HIP call, `SwinBlock.fused_ffn_train`'s
+route (`SwinBlock.fused_ffn_train_wide`'s at C = 512).  C = 1024 has no training operator."""
 import sys
 import types
 
 import torch
 
-from . import _ffn, _ffn_train, _ffn_wide, _lib
+from . import _ffn, _ffn_train, _ffn_wide, _ffn_wide_train, _lib
 from .trace import traced
 
 _F32, _F16, _BF16 = torch.float32, torch.float16, torch.bfloat16
@@ -130,7 +131,7 @@ def swin_ffn_infer(x, norm_weight, norm_bias, eps, w1, b1, w2, b2, mm_dtype=None
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# Training: forward with the DropPath factor, recompute backward (C = 128 and 256)
+# Training: forward with the DropPath factor, recompute backward (C = 128 and 256; C = 512 through the wide training family)
 
 # Which (C, x dtype, GEMM dtype) entries `swin_ffn_train_supported` routes to `swin_ffn`, by ROUTED's rule applied to forward +
 # backward (both weight packs and the torch weight-gradient GEMMs included) against both parents with torch autograd at DHD-L's
@@ -170,6 +171,54 @@ def swin_ffn_train_supported(x, hidden, mm_dtype=None):
     return ROUTED_TRAIN.get((x.shape[-1], x.dtype, mm_dtype or x.dtype), False)
 
 
+# The wide training family (C = 512: DHD-L's stage 2, csrc/swin_ffn_wide_train.h), `SwinBlock.fused_ffn_train_wide`'s table, by
+# ROUTED_TRAIN's rule: an entry is True only where forward + backward beat both parents by more than the largest min-max spread
+# of the three paths at 33 792 x 512, 12 images, DropPath active (experiments/swin_ffn_train_wide_bench.py ->
+# profiles/r17/swin_ffn_train_wide.json).  Medians in us per forward + backward, fused against today / today with fused_glue's
+# norm2 (largest min-max spread of the three paths); with half tokens there is no cast for the glue's norm2 to fuse, so both
+# parents are the same code there and their difference is run-to-run noise:
+#   bf16 autocast 1342 against 1408 / 1347 (45), fp16 autocast 1370 against 1404 / 1356 (66), float32 2617 against 3817 / 3808 (33),
+#   bf16 tokens 1342 against 1420 / 1383 (52), fp16 tokens 1349 against 1422 / 1391 (42)
+# The forward alone wins everywhere (251 / 258 / 567 / 251 / 259 against 335 / 332 / 1312 / 378 / 369 for the better parent); with
+# half GEMMs the backward gives that back: 528 workgroups of 64 rows are 2.06 rounds on 256 CUs.  float32 wins by 1191 us.  fp16
+# tokens win by 42.2 us against a spread of 41.8: True by the rule, by the narrowest of margins.  bf16 tokens -- what DHD-L's
+# backbone hands stage 2 under bf16 autocast -- win by 41 us, less than that run's spread: False, as are the two autocast forms
+# with float32 tokens (a tie, and a loss of 14 us to the glue parent).  The operator itself takes every entry when called directly.
+# (Under checkpointing a block's forward runs twice, which this rule counts once: with every entry forced the DHD-L bf16 step is
+# 235.0 against 236.6 ms, profiles/r17/e2e_dhdl_bf16_swin_ffn_train_wide_forced_ab.json.  The table follows the rule.)
+ROUTED_TRAIN_WIDE = {
+    (512, _F32, _BF16): False, (512, _F32, _F16): False, (512, _F32, _F32): True,
+    (512, _BF16, _BF16): False, (512, _F16, _F16): True,
+}
+
+
+def swin_ffn_train_wide_shape_supported(x, hidden, mm_dtype=None):
+    """True when `swin_ffn`'s wide family takes the tokens `x` (..., C) with `hidden` units in `mm_dtype` (default x's dtype): a
+    GPU tensor, C == 512, hidden == 2048, float32 tokens with any GEMM dtype or half tokens with their own."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.numel() > 0):
+        return False
+    mm_dtype = mm_dtype or x.dtype
+    if x.dtype not in _lib.DTYPE_CODE or mm_dtype not in _lib.DTYPE_CODE:
+        return False
+    return bool(_ffn_wide_train.value('dhdu_swin_ffn_wide_supported', x.shape[-1], int(hidden), _lib.DTYPE_CODE[x.dtype],
+                                      _lib.DTYPE_CODE[mm_dtype]))
+
+
+def swin_ffn_train_wide_supported(x, hidden, mm_dtype=None):
+    """True when a `SwinBlock` with `fused_ffn_train_wide` on sends the tokens `x` (..., C) to `swin_ffn`: the wide family takes
+    them (swin_ffn_train_wide_shape_supported) and the measurement routed that dtype combination to it (ROUTED_TRAIN_WIDE)."""
+    if not swin_ffn_train_wide_shape_supported(x, hidden, mm_dtype):
+        return False
+    return ROUTED_TRAIN_WIDE.get((x.shape[-1], x.dtype, mm_dtype or x.dtype), False)
+
+
+def _train_family(C):
+    """(binding, entry-point stem) of the training family that takes C channels."""
+    if C == 512:
+        return _ffn_wide_train, 'dhdu_swin_ffn_wide'
+    return _ffn_train, 'dhdt_swin_ffn'
+
+
 def _f32(p):
     return _lib.dense16(p.detach().float())
 
@@ -185,14 +234,15 @@ def _scaled_grad(dout, scale, mm_dtype):
 
 
 def swin_ffn_backward(x, dout, norm_weight, norm_bias, eps, w1, b1, w2, mm_dtype=None, scale=None, operands=True):
-    """One dhdt_swin_ffn_backward call on dense, aligned GPU tensors: x, dout (..., C) of one dtype, the parameters as swin_ffn
-    takes them (b2 has no part), scale float32 (images,) or None -> (dx, dgamma, dbeta, xn, act, dhid): dx in x's dtype and shape,
-    dgamma and dbeta float32 (C,), and with `operands` the weight-gradient operands xn (rows, C), act and dhid (rows, 4C) in
+    """One dhdt_swin_ffn_backward (C = 512: dhdu_swin_ffn_wide_backward) call on dense, aligned GPU tensors: x, dout (..., C) of
+    one dtype, the parameters as swin_ffn takes them (b2 has no part), scale float32 (images,) or None -> (dx, dgamma, dbeta, xn,
+    act, dhid): dx in x's dtype and shape, dgamma and dbeta float32 (C,), and with `operands` the weight-gradient operands xn (rows, C), act and dhid (rows, 4C) in
     mm_dtype, else three None (the kernel then writes none of them).  Allocates its outputs and its scratch; nothing is cached."""
     mm_dtype = mm_dtype or x.dtype
     C, hidden = x.shape[-1], w1.shape[0]
     rows, dev = x.numel() // C, x.device
     xc, mc = _lib.dtype_code(x.dtype), _lib.dtype_code(mm_dtype)
+    binding, stem = _train_family(C)
     with torch.cuda.device(dev):
         dx = torch.empty_like(x)
         dgamma = torch.empty(C, dtype=torch.float32, device=dev)
@@ -202,35 +252,37 @@ def swin_ffn_backward(x, dout, norm_weight, norm_bias, eps, w1, b1, w2, mm_dtype
             xn = torch.empty((rows, C), dtype=mm_dtype, device=dev)
             act = torch.empty((rows, hidden), dtype=mm_dtype, device=dev)
             dhid = torch.empty((rows, hidden), dtype=mm_dtype, device=dev)
-        nbytes = _ffn_train.value('dhdt_swin_ffn_backward_scratch_bytes', rows, C, hidden, mc)
+        nbytes = binding.value(stem + '_backward_scratch_bytes', rows, C, hidden, mc)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         held = [_f32(p) for p in (norm_weight, norm_bias, w1, b1, w2)]      # a half model's float32 copies live until the call is made
-        _ffn_train.call('dhdt_swin_ffn_backward', _lib.ptr(x), _lib.ptr(dout), *(_lib.ptr(p) for p in held), _lib.ptr(scale),
-                        rows // scale.numel() if scale is not None else 0, _lib.ptr(dx), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                        _lib.ptr(xn), _lib.ptr(act), _lib.ptr(dhid), _lib.ptr(scratch), nbytes, xc, mc, rows, C, hidden, float(eps),
-                        _lib.stream_ptr(dev))
+        binding.call(stem + '_backward', _lib.ptr(x), _lib.ptr(dout), *(_lib.ptr(p) for p in held), _lib.ptr(scale),
+                     rows // scale.numel() if scale is not None else 0, _lib.ptr(dx), _lib.ptr(dgamma), _lib.ptr(dbeta),
+                     _lib.ptr(xn), _lib.ptr(act), _lib.ptr(dhid), _lib.ptr(scratch), nbytes, xc, mc, rows, C, hidden, float(eps),
+                     _lib.stream_ptr(dev))
     return dx, dgamma, dbeta, xn, act, dhid
 
 
 def _forward(x, norm_weight, norm_bias, eps, w1, b1, w2, b2, mm_dtype, scale):
-    """One dhdt_swin_ffn_forward call on a dense, aligned x."""
+    """One dhdt_swin_ffn_forward (C = 512: dhdu_swin_ffn_wide_forward) call on a dense, aligned x."""
     C, hidden = x.shape[-1], w1.shape[0]
     rows, dev = x.numel() // C, x.device
     xc, mc = _lib.dtype_code(x.dtype), _lib.dtype_code(mm_dtype)
+    binding, stem = _train_family(C)
     with torch.cuda.device(dev):
         out = torch.empty(x.shape, dtype=x.dtype, device=dev)
-        nbytes = _ffn_train.value('dhdt_swin_ffn_forward_scratch_bytes', C, hidden, mc)
+        nbytes = binding.value(stem + '_forward_scratch_bytes', C, hidden, mc)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         held = [_f32(p) for p in (norm_weight, norm_bias, w1, b1, w2, b2)]  # a half model's float32 copies live until the call is made
-        _ffn_train.call('dhdt_swin_ffn_forward', _lib.ptr(x), *(_lib.ptr(p) for p in held), _lib.ptr(scale),
-                        rows // scale.numel() if scale is not None else 0, _lib.ptr(out), _lib.ptr(scratch), nbytes, xc, mc, rows,
-                        C, hidden, float(eps), _lib.stream_ptr(dev))
+        binding.call(stem + '_forward', _lib.ptr(x), *(_lib.ptr(p) for p in held), _lib.ptr(scale),
+                     rows // scale.numel() if scale is not None else 0, _lib.ptr(out), _lib.ptr(scratch), nbytes, xc, mc, rows,
+                     C, hidden, float(eps), _lib.stream_ptr(dev))
     return out
 
 
 class _SwinFFN(torch.autograd.Function):
     """out = x + scale * ffn(norm2(x)); saves the dense x, the parameters and scale, and nothing else: the backward recomputes
-    the hidden tile by tile in dhdt_swin_ffn_backward and leaves the four weight-gradient reductions to torch's GEMMs."""
+    the hidden tile by tile in dhdt_swin_ffn_backward (C = 512: chunk by chunk in dhdu_swin_ffn_wide_backward) and leaves the
+    four weight-gradient reductions to torch's GEMMs."""
 
     @staticmethod
     def forward(ctx, x, norm_weight, norm_bias, w1, b1, w2, b2, scale, eps, mm_dtype):
@@ -273,7 +325,8 @@ def swin_ffn(x, norm_weight, norm_bias, eps, w1, b1, w2, b2, mm_dtype=None, scal
     them: DropPath's floor(keep + rand) / keep), multiplies the branch in float32 before the residual add; None means 1, and
     then the forward returns swin_ffn_infer's bytes.
 
-    The forward saves the dense x, the parameters and scale.  The backward is one dhdt_swin_ffn_backward call, which recomputes
+    C = 128 and 256 run the dhdt_* family, C = 512 the dhdu_* family; C = 1024 has no training operator.
+    The forward saves the dense x, the parameters and scale.  The backward is one backward call of the family, which recomputes
     the hidden tile by tile and returns dx, dgamma, dbeta and -- where a weight or bias wants a gradient -- the operands xn, act
     and dhid in mm_dtype, from which torch's GEMMs take dW1 = dhid^T @ xn, db1 = sum dhid, dW2 = gs^T @ act, db2 = sum gs (gs the
     scaled gradient in mm_dtype), each cast to its parameter's dtype.  No atomics: a repeated call gives the same bytes.  Works
@@ -283,7 +336,7 @@ def swin_ffn(x, norm_weight, norm_bias, eps, w1, b1, w2, b2, mm_dtype=None, scal
         raise _lib.DhdError(f'swin_ffn: x must live on the GPU: dhd_amd runs only as HIP kernels (got {getattr(x, "device", None)})')
     mm_dtype = mm_dtype or x.dtype
     C, hidden = x.shape[-1], w1.shape[0]
-    if not swin_ffn_train_shape_supported(x, hidden, mm_dtype):
+    if not (swin_ffn_train_shape_supported(x, hidden, mm_dtype) or swin_ffn_train_wide_shape_supported(x, hidden, mm_dtype)):
         raise _lib.DhdError(f'swin_ffn: no operator for tokens {tuple(x.shape)} of {x.dtype}, hidden {hidden}, GEMMs in {mm_dtype}')
     for p, shape, name in ((norm_weight, (C,), 'norm_weight'), (norm_bias, (C,), 'norm_bias'), (w1, (hidden, C), 'w1'),
                            (b1, (hidden,), 'b1'), (w2, (C, hidden), 'w2'), (b2, (C,), 'b2')):

@@ -35,7 +35,7 @@ from dhd_amd.swin import FFN
 from dhd_amd.swin_glue import layer_norm_rows, swin_glue_supported
 
 B, EPS, KEEP = 12, 1e-5, 0.9
-STAGES = {0: ((128, 352), 128), 1: ((64, 176), 256)}
+STAGES = {0: ((128, 352), 128), 1: ((64, 176), 256), 2: ((32, 88), 512)}      # stage 2: swin_ffn_train_wide_bench.py's
 F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
 # name -> (stage, token dtype, GEMM dtype)
 CASES = {'stage0_bf16_autocast': (0, F32, BF16), 'stage0_fp16_autocast': (0, F32, F16), 'stage0_f32': (0, F32, F32),
@@ -43,7 +43,8 @@ CASES = {'stage0_bf16_autocast': (0, F32, BF16), 'stage0_fp16_autocast': (0, F32
          'stage1_bf16_tokens': (1, BF16, BF16), 'stage1_fp16_tokens': (1, F16, F16)}
 
 
-def make_case(stage, xdt, mdt, dev):
+def make_case(stage, xdt, mdt, dev, supported=swin_ffn.swin_ffn_train_shape_supported):
+    """`supported`: the predicate of the training family that takes the stage's C."""
     (H, W), C = STAGES[stage]
     rows = B * H * W
     torch.manual_seed(7 + stage)
@@ -66,7 +67,7 @@ def make_case(stage, xdt, mdt, dev):
     forms = {'today': lambda: x + drop(ffn.layers(norm(x)))}
     glue = swin_glue_supported(x, plain_ln_to=mdt)       # as SwinBlock._forward_glue asks: where there is no cast to fuse, torch's norm2
     forms['today_glue'] = (lambda: x + drop(ffn.layers(layer_norm_rows(x, norm.weight, norm.bias, EPS, mdt)))) if glue else forms['today']
-    if swin_ffn.swin_ffn_train_shape_supported(x, 4 * C, mdt):
+    if supported(x, 4 * C, mdt):
         forms['fused'] = lambda: swin_ffn.swin_ffn(x, norm.weight, norm.bias, EPS, fc1.weight, fc1.bias, fc2.weight, fc2.bias, mdt, scale)
 
     def forward(f):
