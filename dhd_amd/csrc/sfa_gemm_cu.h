@@ -94,13 +94,20 @@ __device__ __forceinline__ void cu_pack_weight(const float* __restrict__ w, int 
 // 8 no activation loads (stale registers are staged), 16 no staging, 32 no B-fragment LDS reads (MFMAs on registers),
 // 64 shader clocks of the workgroup (s_memtime) into stat_part, 128 s_sleep in place of the MFMAs (with 1), 256 shader clocks per
 // phase and wave into stat_part
+// WB (data gradients, EPI 1 / 2): the staging lane that loaded a row's 16 bytes stores the float32 prologue result c0*in0 + c1*in1
+// + c2 back over them (before the bf16 cut), through `wb` -- in0's buffer as a plain pointer; in0 itself is not read then.  The
+// weight gradient that follows reads that ONE tensor instead of re-applying the prologue to the pair (sfa_stage.hip: fold).  The
+// stores are plain (non-temporal ones measured 4 - 15 us slower on the step, LAB_NOTEBOOK R18), and a tile is written back
+// by its FIRST staging only: the repeated last tile would apply the prologue to its own output, so its
+// stores (and those of pixel quads beyond the row's end) go out of the buffer's range like the epilogue's.
 template <int KCN, int WAVES, bool TWO_IN, bool RELU, int EPI, bool RECORD, int AUX, int R, int NACC, int ABL = 0, int SAUX = 0, bool PP = false,
-          int BPF = 0, int EORD = 0, class TO = float>
+          int BPF = 0, int EORD = 0, class TO = float, bool WB = false>
 __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* __restrict__ in0, const float* __restrict__ in1,
                                                                    size_t in_bstride, unsigned in_bytes, const float* __restrict__ coef,
                                                                    const u32x4* __restrict__ wp, const float* __restrict__ bias,
                                                                    unsigned* __restrict__ relu_mask, float* __restrict__ stat_part,
-                                                                   float* __restrict__ y, int hw, int nb, int contig, CuBlend bl) {
+                                                                   float* __restrict__ y, int hw, int nb, int contig, CuBlend bl, float* wb = nullptr) {
+  static_assert(!WB || (TWO_IN && !RELU && (EPI == 1 || EPI == 2) && ABL == 0), "write-back: the BatchNorm-backward prologue of a data gradient");
   constexpr int C = 16 * KCN;
   constexpr int MT = C / (32 * WAVES);          // 32-channel output tiles (= 32-row input groups) per wave
   static_assert(MT >= 1 && MT * 32 * WAVES == C, "C = 32 * MT * WAVES");
@@ -172,7 +179,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
     t = min(t, t_last);
     const int b = t / nwt, wt = t - b * nwt, p0 = wt * 32;
     const __amdgpu_buffer_rsrc_t s0 =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in0 + (size_t)b * in_bstride), 0, in_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(WB ? wb + (size_t)b * in_bstride : const_cast<float*>(in0 + (size_t)b * in_bstride), 0, in_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t s1 =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>((TWO_IN ? in1 : in0) + (size_t)b * in_bstride), 0, in_bytes, 0x00020000);
     // a pixel quad beyond the row's end (last tile, hw % 32 != 0) re-reads quad 0: its columns are never stored or summed
@@ -192,6 +199,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
   float abl_sink = 0.f;
   auto stage = [&](auto slotc, int buf, int t) {
     constexpr int S = decltype(slotc)::value;
+    const int t_asked = t;                                           // (WB: beyond t_last = the last tile over again)
     t = min(t, t_last);
     unsigned char* dst = cu_lds + buf * BUFB;
     const float* cb = cf_lds + (t / nwt) * 3 * C + kbase + 4 * g;
@@ -215,6 +223,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
           if (TWO_IN) tv = fmaf(c1[j], r1[S][rg][j][e], tv);
           v[j] = RELU ? fmaxf(tv, 0.f) : tv;
           if (RECORD) bits |= min(__float_as_uint(v[j]), 1u) << (4 * j + e);   // v >= 0 here: v > 0 <=> its bits != 0
+          if constexpr (WB) r0[S][rg][j][e] = tv;                    // (the raw value is dead from here on)
         }
         unsigned h01, m01, h23, m23;
         split2_hm(v[0], v[1], h01, m01);
@@ -224,6 +233,14 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pw_gemm_cu_kernel(const float* 
         asm("v_xor_b32 %0, %1, %2" : "=v"(wa) : "n"(cu_swz_c(e) << 4), "v"(wbase[rg]));
         *reinterpret_cast<u32x2*>(dst + wa + e * ROWB) = hq;
         *reinterpret_cast<u32x2*>(dst + wa + e * ROWB + PARTB) = mq;
+      }
+      if constexpr (WB) {                                            // the prologue's result back over the rows as loaded
+        const int b = t / nwt, p0 = (t - b * nwt) * 32;
+        const __amdgpu_buffer_rsrc_t sw = __builtin_amdgcn_make_buffer_rsrc(wb + (size_t)b * in_bstride, 0, in_bytes, 0x00020000);
+        const int voff_wb = (t_asked <= t_last && p0 + 4 * q < hw) ? ld_voff : 0x7ffffff0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          store_b128_guarded<0>(__builtin_bit_cast(u32x4, r0[S][rg][j]), sw, voff_wb, (32 * rg + j) * row_bytes + p0 * 4);
       }
       if (RECORD && !(ABL & 16))
         reinterpret_cast<unsigned short*>(relu_mask)[((size_t)t * (C / 32) + wv * MT + rg) * 64 + lane] = (unsigned short)bits;

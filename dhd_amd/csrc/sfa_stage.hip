@@ -22,6 +22,22 @@
 //   * BatchNorm gradient sums are per-plane streaming reductions with double-precision finalisation; the blends are fused with
 //     the BatchNorm affine and the sigmoid.
 // Forward reads x three times and y1/y2 twice; nothing is transposed, there is no NHWC detour.
+// Backward, bf16x3 at C = 128 / 256 on float32 storage without cross-rank statistics (the FOLDED flow, DHD_SFA_BWD_FOLD = 3, the
+// default; T = one (B,C,H,W) tensor).  Both GEMMs of a layer apply the same BatchNorm-backward prologue gy = c0 g + c1 y + c2, so
+// the data gradient runs FIRST and stores gy over g, and the weight gradient reads that one tensor; the load stream this frees
+// carries the tensor a reduction pass of its own used to re-read:
+//   launch                          reads                          writes
+//   blend2_bn_bwd                   x (2T), y2, gout               g2; BatchNorm-2 sums, go-part of dL/da
+//   pw_gemm_cu EPI 1, WB (dgrad 2)  g2, y2, pass bits              g1, gy2 over g2
+//   pw_wgrad3 FOLD 1 (dW2)          gy2, y1, g1                    partials; sum g1, sum g1 (y1 - mu1) per worker
+//   wgrad_reduce, bn_backward_rows  partials, worker rows          dW2; BatchNorm-1 backward table, dgamma1, dbeta1
+//   pw_gemm_cu EPI 2, WB (dgrad 1)  g1, y1                         du, gy1 over g1
+//   pw_wgrad3 FOLD 2 (dW1)          gy1, x (2T), du                partials; sum du (x_bev - x_voxel) per (worker, sample)
+//   wgrad_reduce, fc_backward       partials, worker rows          dW1; dL/d(fc)
+//   stage_gx                        y2, gout, du                   gx (2T)
+// 18T of reads and 7T of writes.  The unfolded flow (every other plan, the phase entry points, DHD_SFA_BWD_FOLD = 0) runs each
+// weight gradient before its data gradient on the pair (g, y) and makes the sums in pair_sums (g1, y1) and blend1_da (x, du):
+// 23T of reads, 5T of writes.
 // Forward-only inference (dhd_sfa_stage_infer, running statistics, nothing kept for a backward): stage_infer below -- the forward's
 // own launches, conv2 with BatchNorm-2 + sigmoid + blend in its epilogue (x three times, y1 twice), or under half storage both
 // convolutions per pixel tile (sfa_half.h: sfa_onepass_h_kernel; x twice).
@@ -44,6 +60,15 @@ constexpr int kPwStep = 16;       // input channels per weight image / pipeline 
 constexpr int kWgBlock = 512;     // pw_wgrad: 8 waves
 constexpr int kWgStride = 33;     // LDS row stride of a 32-pixel operand row (conflict-free column reads)
 constexpr int kWgWorkers = 256;   // total pw_wgrad blocks (one per CU)
+// The weight gradients' split of n steps (32 pixels each, sample after sample) over W workers, in ONE place for the kernel that
+// works by it (pw_wgrad3_kernel) and the kernel that reads per-(worker, sample) rows back (fc_backward_kernel): worker w owns the
+// steps [wg_first_step(n, w, W), wg_first_step(n, w + 1, W)), so step s belongs to worker wg_owner(n, s, W).
+__host__ __device__ inline long long wg_first_step(long long n, long long w, long long W) { return n * w / W; }
+__host__ __device__ inline int wg_owner(long long n, long long s, long long W) { return (int)(((s + 1) * W + n - 1) / n) - 1; }
+// operand blocks and workers per block of a weight-gradient launch (launch_wgrad) at c channels
+inline int wgrad_blocks(int c) { const int ot = c == 128 ? 128 : 256; return (c / ot) * (c / ot); }
+inline int wgrad_workers(int c) { const int nob = wgrad_blocks(c); return kWgWorkers / nob > 0 ? kWgWorkers / nob : 1; }
+constexpr int kBwdFoldDefault = 3;  // DHD_SFA_BWD_FOLD when the environment does not say (bwd_fold_mode)
 
 __device__ __forceinline__ float block_sum(float v, float* sm) {
   v = group_sum(v, DHD_WAVE);
@@ -261,15 +286,33 @@ __global__ __launch_bounds__(kEwBlock) void fc_backward_kernel(const float* __re
                                                                const float* __restrict__ a, const float* __restrict__ hbuf,
                                                                const float* __restrict__ w1, const float* __restrict__ w2,
                                                                float* __restrict__ dpre2, float* __restrict__ dh,
-                                                               float* __restrict__ ds, int c, int r) {
+                                                               float* __restrict__ ds, int c, int r, int fold_workers, int sps) {
   extern __shared__ float sh[];  // dpre2 (c) | dh (r) | partials (kEwBlock)
   float* sp = sh;
   float* sd = sh + c;
   const int b = blockIdx.x, c2 = 2 * c;
+  // fold_workers > 0: da_p2 holds the rows of the folded conv1 weight gradient (pw_wgrad3_kernel, FOLD 2): row w + b from worker w
+  // for sample b, for every worker from the owner of the sample's first step to the owner of its last
+  const long long n = (long long)gridDim.x * sps;
+  const int w_lo = fold_workers > 0 ? wg_owner(n, (long long)b * sps, fold_workers) : 0;
+  const int w_hi = fold_workers > 0 ? wg_owner(n, (long long)(b + 1) * sps - 1, fold_workers) : -1;
   for (int k = threadIdx.x; k < c; k += kEwBlock) {
     float g = 0.f;
-    for (int q = 0; q < kPlaneChunks; ++q)
-      g += da_p1[((size_t)b * kPlaneChunks + q) * c + k] + da_p2[((size_t)b * kPlaneChunks + q) * c + k];
+    if (fold_workers > 0) {
+      for (int q = 0; q < kPlaneChunks; ++q) g += da_p1[((size_t)b * kPlaneChunks + q) * c + k];
+      double g2 = 0.0;
+      for (int w0 = w_lo; w0 <= w_hi; w0 += 32) {   // 32 rows in flight together; the sum keeps the order of the plain loop
+        float v[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) v[u] = da_p2[(size_t)(min(w0 + u, w_hi) + b) * c + k];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) g2 += w0 + u <= w_hi ? (double)v[u] : 0.0;
+      }
+      g += (float)g2;
+    } else {
+      for (int q = 0; q < kPlaneChunks; ++q)
+        g += da_p1[((size_t)b * kPlaneChunks + q) * c + k] + da_p2[((size_t)b * kPlaneChunks + q) * c + k];
+    }
     const float av = a[(size_t)b * c + k];
     const float v = g * av * (1.0f - av);
     sp[k] = v;
@@ -484,6 +527,40 @@ __global__ __launch_bounds__(kEwBlock) void bn_eval_coef2_kernel(BnEvalJob j1, B
 //   training: dy = gamma*rstd*(g - S1/n - (y-mu)*rstd^2*S2/n);  eval: dy = gamma*rstd*g
 // COHERENT: the partial sums were written by other workgroups of the SAME launch (see BnTail): read them past the
 // non-coherent cache levels.
+// the channel's coefficients, dgamma, dbeta and bias gradient from its two sums s1 = sum g, s2 = sum g (y - mu)
+__device__ __forceinline__ void bn_backward_coef_from_sums(double s1, double s2, int ch, const float* __restrict__ gamma,
+                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                           int training, float* __restrict__ tab, float* __restrict__ dgamma,
+                                                           float* __restrict__ dbeta, float* __restrict__ dbias, int nb, int c, int hw,
+                                                           double* __restrict__ sums_out, const double* __restrict__ sums_in,
+                                                           const double* __restrict__ loc_fwd, const float* __restrict__ shift) {
+  const double n_loc = (double)nb * (double)hw;
+  if (sums_out) {
+    sums_out[ch] = s1; sums_out[c + ch] = s2;
+    if (ch == 0) sums_out[2 * c] = n_loc;
+    return;
+  }
+  const double n = sums_in ? sums_in[2 * c] : n_loc;
+  const double g1 = sums_in ? sums_in[ch] : s1, g2 = sums_in ? sums_in[c + ch] : s2;
+  const double rs = (double)rstd[ch], mu = (double)mean[ch], ga = (double)gamma[ch];
+  if (dgamma) dgamma[ch] = (float)(rs * s2);
+  if (dbeta) dbeta[ch] = (float)s1;
+  double c0 = ga * rs, c1 = 0.0, c2 = 0.0, db = c0 * s1;
+  if (training) {
+    c1 = -ga * rs * rs * rs * g2 / n;
+    c2 = -ga * rs * g1 / n - c1 * mu;
+    db = 0.0;  // sum of dy over the (whole) batch vanishes identically
+    if (sums_in) db = c0 * s1 + c1 * (loc_fwd[ch] + n_loc * (double)shift[ch]) + n_loc * c2;
+  }
+  if (dbias) dbias[ch] = (float)db;
+  for (int b = 0; b < nb; ++b) {
+    float* t = tab + (size_t)b * 3 * c;
+    t[ch] = (float)c0;
+    t[c + ch] = (float)c1;
+    t[2 * c + ch] = (float)c2;
+  }
+}
+
 template <bool COHERENT>
 __device__ __forceinline__ void bn_backward_coef_channel(const float* __restrict__ part, int ch, const float* __restrict__ gamma,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -517,32 +594,19 @@ __device__ __forceinline__ void bn_backward_coef_channel(const float* __restrict
       s2 += (double)part[((size_t)q * 2 + 1) * c + ch];
     }
   }
-  const double n_loc = (double)nb * (double)hw;
-  if (sums_out) {
-    sums_out[ch] = s1; sums_out[c + ch] = s2;
-    if (ch == 0) sums_out[2 * c] = n_loc;
-    return;
-  }
-  const double n = sums_in ? sums_in[2 * c] : n_loc;
-  const double g1 = sums_in ? sums_in[ch] : s1, g2 = sums_in ? sums_in[c + ch] : s2;
-  const double rs = (double)rstd[ch], mu = (double)mean[ch], ga = (double)gamma[ch];
-  if (dgamma) dgamma[ch] = (float)(rs * s2);
-  if (dbeta) dbeta[ch] = (float)s1;
-  double c0 = ga * rs, c1 = 0.0, c2 = 0.0, db = c0 * s1;
-  if (training) {
-    c1 = -ga * rs * rs * rs * g2 / n;
-    c2 = -ga * rs * g1 / n - c1 * mu;
-    db = 0.0;  // sum of dy over the (whole) batch vanishes identically
-    if (sums_in) db = c0 * s1 + c1 * (loc_fwd[ch] + n_loc * (double)shift[ch]) + n_loc * c2;
-  }
-  if (dbias) dbias[ch] = (float)db;
-  for (int b = 0; b < nb; ++b) {
-    float* t = tab + (size_t)b * 3 * c;
-    t[ch] = (float)c0;
-    t[c + ch] = (float)c1;
-    t[2 * c + ch] = (float)c2;
-  }
+  bn_backward_coef_from_sums(s1, s2, ch, gamma, mean, rstd, training, tab, dgamma, dbeta, dbias, nb, c, hw, sums_out, sums_in, loc_fwd, shift);
 }
+
+struct BnRowsJob {
+  const float* gamma;
+  const float* mean;
+  const float* rstd;
+  float* tab;
+  float* dgamma;
+  float* dbeta;
+  float* dbias;
+  int training, nb, hw;
+};
 
 __global__ __launch_bounds__(kEwBlock) void bn_backward_coef_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
                                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -555,6 +619,36 @@ __global__ __launch_bounds__(kEwBlock) void bn_backward_coef_kernel(const float*
   if (ch >= c) return;
   bn_backward_coef_channel<false>(part, ch, gamma, mean, rstd, training, tab, dgamma, dbeta, dbias, nb, c, hw, sums_out, sums_in,
                                   loc_fwd, shift);
+}
+
+// The same from the rows [n_rows][2][c] a folded weight-gradient kernel left (pw_wgrad3_kernel, FOLD 1: one row per worker).  A
+// workgroup owns four channels, as in bn_stats_finalize_kernel: thread t sums rows t, t + 256, ... with one 16-byte load per sum,
+// the 256 partial sums meet in LDS as doubles (fixed tree), threads 0-3 finalize one channel each.
+__global__ __launch_bounds__(kEwBlock) void bn_backward_rows_kernel(const float* __restrict__ rows, int n_rows, BnRowsJob j, int c) {
+  __shared__ double sm[kEwBlock][8];
+  const int t = threadIdx.x, ch0 = 4 * blockIdx.x;
+  const size_t row4 = (size_t)(2 * c) / 4;
+  const f32x4* p1 = reinterpret_cast<const f32x4*>(rows + ch0);
+  const f32x4* p2 = reinterpret_cast<const f32x4*>(rows + c + ch0);
+  double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = t; i < n_rows; i += kEwBlock) {
+    const f32x4 v1 = p1[(size_t)i * row4], v2 = p2[(size_t)i * row4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { a[e] += (double)v1[e]; a[4 + e] += (double)v2[e]; }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) sm[t][e] = a[e];
+  __syncthreads();
+  for (int s = kEwBlock / 2; s > 0; s >>= 1) {
+    if (t < s) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sm[t][e] += sm[t + s][e];
+    }
+    __syncthreads();
+  }
+  if (t >= 4) return;
+  bn_backward_coef_from_sums(sm[0][t], sm[0][4 + t], ch0 + t, j.gamma, j.mean, j.rstd, j.training, j.tab, j.dgamma, j.dbeta, j.dbias, j.nb,
+                             c, j.hw, nullptr, nullptr, nullptr, nullptr);
 }
 
 // The coefficient kernel above as the TAIL of the pass that produces its sums (one launch and ~7 us of latency chain less
@@ -927,12 +1021,31 @@ __global__ __launch_bounds__(kEwBlock) void bn_stats_finalize_kernel(const float
 //     touched per instruction, each line touched by four instructions).  An 8-pixel item is then assembled with one
 //     lane-pair exchange (DPP quad_perm): of the rows loaded by instructions 2a and 2a+1, the even lane keeps its piece
 //     of row 2a and takes its neighbour's, the odd lane does the same for row 2a+1.
-template <int OT, bool A_TWO, bool B_TWO, bool B_RELU>
+//
+// FOLD (stage_backward's folded flow; one operand block, c == OT): the data gradient that ran before this kernel left the
+// BatchNorm-backward prologue's result in a0, so A is ONE input without a prologue, and the load stream that frees carries `aux`,
+// a (nb, C, hw) tensor read at the B rows' addresses by the lanes that load them (before the pair exchange: 8 lanes = one row's
+// line), for a per-row reduction a pass of its own used to make:
+//   1  aux = g1, B = y1:            sum aux, sum aux*(y1 - mean[row]) (pair_sums_kernel's terms) -> fold_part[worker][2][c]
+//   2  aux = du, B = x_bev|x_voxel: sum aux*(x_bev - x_voxel) per SAMPLE (blend1_da_kernel's term) -> fold_part[worker + sample][c]
+//      (a worker's steps are contiguous, so worker + sample names each (worker, sample) pair that occurs exactly once)
+// A and B are loaded non-temporally in this form and aux plainly: du is read once more by stage_gx right after the conv1 weight
+// gradient, and with all four tensors loaded plainly the 4T of this kernel push it out of the last-level cache (stage_gx 128 ->
+// 149 us, the step 16 us SLOWER than the unfolded flow; with the hint 47 us faster: LAB_NOTEBOOK R18).
+// Per-thread accumulators over the worker's steps; the 8 lanes of a row meet in a fixed shuffle order: no atomics, the same bytes
+// on every call.  The repeated last step (step_of) and pixel quads beyond the row's end add nothing.
+template <int OT, bool A_TWO, bool B_TWO, bool B_RELU, int FOLD = 0>
 __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __restrict__ a0, const float* __restrict__ a1,
                                                                 const float* __restrict__ acoef, size_t a_bstride,
                                                                 const float* __restrict__ b0, const float* __restrict__ b1,
                                                                 const float* __restrict__ bcoef, size_t b_bstride,
-                                                                float* __restrict__ partial, int c, int hw, int nb, int n_workers) {
+                                                                float* __restrict__ partial, int c, int hw, int nb, int n_workers,
+                                                                const float* __restrict__ aux = nullptr,
+                                                                const float* __restrict__ aux_mean = nullptr,
+                                                                float* __restrict__ fold_part = nullptr) {
+  static_assert(FOLD == 0 || !A_TWO, "fold: A comes without a prologue");
+  static_assert(FOLD != 1 || !B_TWO, "fold 1: B is y1");
+  static_assert(FOLD != 2 || B_TWO, "fold 2: B is x_bev | x_voxel");
   constexpr int TA = OT / 64, TB = OT / 128;     // 32x32 tiles per wave
   constexpr int kTiles = OT / 32;                // 32-row tiles per operand
   constexpr int kOp = kTiles * 2 * 64;           // 16-byte units of one staged operand k-step: [tile][term][lane]
@@ -950,8 +1063,8 @@ __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __r
   // worker w takes the contiguous range [n_steps w / n_workers, n_steps (w + 1) / n_workers).  (Tried: steps w, w + n_workers,
   // ... so that at any moment the workers together read one contiguous span of every channel row: 141 / 130 vs 133 / 128 us.)
   const int w_id = blockIdx.x;
-  const int first = (int)(n_steps * w_id / n_workers);
-  const int count = (int)(n_steps * (w_id + 1) / n_workers) - first;
+  const int first = (int)wg_first_step(n_steps, w_id, n_workers);
+  const int count = (int)wg_first_step(n_steps, w_id + 1, n_workers) - first;
   auto step_of = [&](int k) { return first + min(k, count - 1); };   // past the end: the last step again
 
   // loads: instruction j reads rows 64 j + 8 wv + (lane >> 3), four pixels 4 (lane & 7) ..
@@ -969,16 +1082,48 @@ __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __r
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
   f32x4 raw[2][2][NJ];                           // [operand][input][load instruction]
-  float cfa[NA][3], cfb[NA][3];                  // prologue coefficients of this thread's item rows
+  float cfa[NA][3], cfb[NA][3];                  // prologue coefficients of this thread's item rows (FOLD: cfa is unused)
+  auto coef = [&](int op, int a, int q) {
+    if constexpr (FOLD != 0) return cfb[a][q];   // A is staged as loaded: only B asks
+    else return op ? cfb[a][q] : cfa[a][q];
+  };
   int cur_b = -1;
+  // FOLD: the auxiliary rows of load instruction j (row 64 j + ld_row, this lane's four pixels) and their running sums
+  f32x4 rawx[FOLD ? NJ : 1];
+  float fs1[FOLD ? NJ : 1], fs2[FOLD == 1 ? NJ : 1], fmu[FOLD == 1 ? NJ : 1];
+  if constexpr (FOLD != 0) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      fs1[j] = 0.f;
+      if constexpr (FOLD == 1) { fs2[j] = 0.f; fmu[j] = aux_mean[ob_ci + 64 * j + ld_row]; }
+    }
+  }
+  // FOLD 2: the sums of sample bs are complete -> this worker's row of that sample
+  auto fold_flush = [&](int bs) {
+    if constexpr (FOLD == 2) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        float v = fs1[j];
+        v += __shfl_xor(v, 1, DHD_WAVE);
+        v += __shfl_xor(v, 2, DHD_WAVE);
+        v += __shfl_xor(v, 4, DHD_WAVE);
+        if ((lane & 7) == 0) fold_part[(size_t)(blockIdx.x + bs) * c + ob_ci + 64 * j + ld_row] = v;
+        fs1[j] = 0.f;
+      }
+    }
+  };
   auto load_coefs = [&](int b) {
+    if (FOLD == 2 && cur_b >= 0) fold_flush(cur_b);
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
       const int row = 64 * (2 * a + odd) + ld_row;
-      const float* ca = acoef + (size_t)b * 3 * c + ob_co + row;
+      [[maybe_unused]] const float* ca = FOLD == 0 ? acoef + (size_t)b * 3 * c + ob_co + row : nullptr;   // FOLD: A has no prologue
       const float* cb = bcoef + (size_t)b * 3 * c + ob_ci + row;
 #pragma unroll
-      for (int q = 0; q < 3; ++q) { cfa[a][q] = ca[q * c]; cfb[a][q] = cb[q * c]; }
+      for (int q = 0; q < 3; ++q) {
+        if constexpr (FOLD == 0) cfa[a][q] = ca[q * c];
+        cfb[a][q] = cb[q * c];
+      }
     }
     cur_b = b;
   };
@@ -993,23 +1138,52 @@ __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __r
       const size_t base = (size_t)b * (op ? b_bstride : a_bstride) + (size_t)((op ? ob_ci : ob_co) + ld_row) * hw + off;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
+        if (FOLD != 0) {   // streamed once and not again in this backward: keep them out of the way of aux (header comment)
+          raw[op][0][j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src0 + base + (size_t)(64 * j) * hw));
+          if (two) raw[op][1][j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src1 + base + (size_t)(64 * j) * hw));
+          continue;
+        }
         raw[op][0][j] = *reinterpret_cast<const f32x4*>(src0 + base + (size_t)(64 * j) * hw);
         if (two) raw[op][1][j] = *reinterpret_cast<const f32x4*>(src1 + base + (size_t)(64 * j) * hw);
       }
     }
+    if constexpr (FOLD != 0) {
+      const size_t base = ((size_t)b * c + ob_ci + ld_row) * hw + off;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) rawx[j] = *reinterpret_cast<const f32x4*>(aux + base + (size_t)(64 * j) * hw);
+    }
   };
   // neighbour lane's value (lanes 2k <-> 2k+1): DPP quad_perm [1,0,3,2]
   auto swap1 = [](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true)); };
-  auto stage = [&](int s, int buf) {
+  // live (FOLD): the first staging of step s, not the last step over again
+  auto stage = [&](int s, int buf, bool live) {
     const int b = s / sps, p = (s % sps) * 32 + 8 * chunk;
     if (b != cur_b) load_coefs(b);  // block-uniform, a few times per worker
     const bool in_lo = p < hw, in_hi = p + 4 < hw;
+    if constexpr (FOLD != 0) {      // on the rows as loaded: pairwise over the four pixels, plain multiplies (float32 storage's fold)
+      const bool ok = live && (s % sps) * 32 + ld_px < hw;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const f32x4 d = rawx[j], y = raw[1][0][j];
+        if constexpr (FOLD == 1) {
+          const float mu = fmu[j];
+          const float t1 = (d.x + d.y) + (d.z + d.w);
+          const float t2 = (d.x * (y.x - mu) + d.y * (y.y - mu)) + (d.z * (y.z - mu) + d.w * (y.w - mu));
+          fs1[j] += ok ? t1 : 0.f;
+          fs2[j] += ok ? t2 : 0.f;
+        } else {
+          const f32x4 v = raw[1][1][j];
+          const float t1 = (d.x * (y.x - v.x) + d.y * (y.y - v.y)) + (d.z * (y.z - v.z) + d.w * (y.w - v.w));
+          fs1[j] += ok ? t1 : 0.f;
+        }
+      }
+    }
 #pragma unroll
     for (int op = 0; op < 2; ++op) {
       const bool two = op ? B_TWO : A_TWO;
 #pragma unroll
       for (int a = 0; a < NA; ++a) {
-        const float k0 = op ? cfb[a][0] : cfa[a][0], k1 = op ? cfb[a][1] : cfa[a][1], k2 = op ? cfb[a][2] : cfa[a][2];
+        const float k0 = coef(op, a, 0), k1 = coef(op, a, 1), k2 = coef(op, a, 2);
         const f32x2 k0v = {k0, k0}, k1v = {k1, k1}, k2v = {k2, k2};
         // assemble the item: [lo 4 pixels | hi 4 pixels] of this thread's row, per input
         float x[2][8];
@@ -1029,7 +1203,7 @@ __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __r
 #pragma unroll
         for (int jp = 0; jp < 4; ++jp) {
           const f32x2 x0 = {x[0][2 * jp], x[0][2 * jp + 1]};
-          f32x2 t = __builtin_elementwise_fma(k0v, x0, k2v);
+          f32x2 t = (FOLD != 0 && op == 0) ? x0 : __builtin_elementwise_fma(k0v, x0, k2v);
           if (two) {
             const f32x2 x1 = {x[1][2 * jp], x[1][2 * jp + 1]};
             t = __builtin_elementwise_fma(k1v, x1, t);
@@ -1050,7 +1224,7 @@ __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __r
 
   if (count > 0) {
     fetch(step_of(0));
-    stage(step_of(0), 0);
+    stage(step_of(0), 0, true);
     fetch(step_of(1));
   }
   __syncthreads();
@@ -1058,7 +1232,7 @@ __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __r
     const int buf = k & 1;
     // unconditional (indices clamped to the last step, whose re-staged copy nobody reads), see pw_wgrad6_kernel.
     // (tried: operand by operand -- stage A(s+1), request A(s+2), stage B(s+1), request B(s+2): no gain)
-    stage(step_of(k + 1), buf ^ 1);
+    stage(step_of(k + 1), buf ^ 1, k + 1 < count);
     fetch(step_of(k + 2));
     // keep the loads of step s + 2 ahead of this step's MFMAs (the scheduler sinks them to the end)
     __builtin_amdgcn_sched_barrier(0);
@@ -1099,6 +1273,25 @@ __global__ __launch_bounds__(kWgBlock, 1) void pw_wgrad3_kernel(const float* __r
         const int ci = ob_ci + wci + 32 * j + r;
         po[(size_t)co * c + ci] = acc[i][j][e];
       }
+  if constexpr (FOLD == 1) {        // one row [2][c] per worker (zeros from a worker without steps)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      float v1 = fs1[j], v2 = fs2[j];
+#pragma unroll
+      for (int m = 1; m < 8; m <<= 1) {
+        v1 += __shfl_xor(v1, m, DHD_WAVE);
+        v2 += __shfl_xor(v2, m, DHD_WAVE);
+      }
+      if ((lane & 7) == 0) {
+        float* row = fold_part + (size_t)blockIdx.x * 2 * c + ob_ci + 64 * j + ld_row;
+        row[0] = v1;
+        row[c] = v2;
+      }
+    }
+  }
+  // the last sample's row; a worker without steps (fewer steps than workers) leaves a row of zeros for the sample its empty range
+  // lies in, so that whoever sums a sample's rows need not know which workers had steps
+  if (FOLD == 2) fold_flush(count > 0 ? cur_b : min(first / sps, nb - 1));
 }
 
 // gw[i] = sum over workers of partial[w][i].  A workgroup covers 64 consecutive elements x 4 worker phases: wave
@@ -1356,6 +1549,7 @@ struct GemmCall {
   const float* aux_scsh;
   CuBlend blend;             // kConv2Blend: x, a, BatchNorm-2 scale / shift, out (y is unused)
   int out_dtype;             // kConv2Blend on float32 storage: element type of blend.out
+  TS* wb;                    // data gradients of the cu kernels, float32 storage: in0 again, to take the prologue's result (or nullptr)
 };
 
 // One-CU-per-pixel-tile kernels: pw_gemm_cu (float32 storage, sfa_gemm_cu.h) and pw_gemm_cuh (half storage, sfa_half.h)
@@ -1407,8 +1601,15 @@ int launch_gemm_cu(const GemmCall<TS>& g, int b, int c, int hw, hipStream_t st, 
         } else {
           auto go = [&](auto* to) {
             using TO = std::remove_pointer_t<decltype(to)>;
+            if constexpr (V::epi == 1 || V::epi == 2) {
+              if (g.wb != nullptr)   // the prologue's result goes back over in0
+                return launch_lds<pw_gemm_cu_kernel<KCN, WAVES, V::two, V::relu, V::epi, V::rec, 2, 1, 1, 0, 0, true, 0, EORD, TO, true>>(
+                    dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb, 1,
+                    bl, g.wb + (size_t)b0 * g.in_bstride);
+            }
             return launch_lds<pw_gemm_cu_kernel<KCN, WAVES, V::two, V::relu, V::epi, V::rec, 2, 1, 1, 0, 0, true, 0, EORD, TO>>(
-                dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb, 1, bl);
+                dim3(grid), dim3(WAVES * 64), shmem, kLdsBytes, st, i0, i1, g.in_bstride, in_bytes, cf, wp, g.bias, rm, sp, yo, hw, nb, 1, bl,
+                static_cast<float*>(nullptr));
           };
           if constexpr (V::epi == 3) {
             if (g.out_dtype == DHD_F16) return go((_Float16*)nullptr);
@@ -1545,12 +1746,21 @@ int launch_gemm(const Plan& p, const GemmCall<TS>& g, int b, int c, int hw, hipS
 // b0 / b1, conv2: BatchNorm + ReLU of b0).  Per-worker partial matrices, reduced deterministically by wgrad_reduce_kernel.
 // (tried at C = 256 in the bf16x3 mode: 128 x 128 tiles, two workgroups per CU, operands read twice through L2: 233 / 189 us
 // against 166 / 138 us for one 256 x 256 tile per CU)
+// fold (Wgrad::w3 on float32 storage, C = 128 / 256): a0 holds the prologue's result already (the data gradient ran first with
+// GemmCall::wb) and the kernel also reduces `aux` along the B rows into `rows` (pw_wgrad3_kernel, FOLD = mode).
+struct WgradFold {
+  int mode;            // 0 none, 1 BatchNorm-1 sums of aux = g1 (mean = mean1), 2 per-sample dL/da sums of aux = du
+  const float* aux;
+  const float* mean;
+  float* rows;
+};
 template <class TS>
 int launch_wgrad(const Plan& p, Op b_of, const TS* a0, const TS* a1, const float* acoef, size_t a_bs, const TS* b0, const TS* b1,
-                 const float* bcoef, size_t b_bs, float* partial, float* gw, int b, int c, int hw, hipStream_t st) {
+                 const float* bcoef, size_t b_bs, float* partial, float* gw, int b, int c, int hw, hipStream_t st,
+                 WgradFold fold = WgradFold{0, nullptr, nullptr, nullptr}) {
   const int ot = c == 128 ? 128 : 256;
-  const int nob = (c / ot) * (c / ot);
-  const int workers = kWgWorkers / nob > 0 ? kWgWorkers / nob : 1;
+  const int nob = wgrad_blocks(c);
+  const int workers = wgrad_workers(c);
   const dim3 grid(workers, nob), block(kWgBlock);
   const int rc = with_op(b_of, [&](auto v) {
     using V = decltype(v);
@@ -1562,8 +1772,15 @@ int launch_wgrad(const Plan& p, Op b_of, const TS* a0, const TS* a1, const float
                                                                      b_bs, partial, c, hw, b, workers);
       } else if (p.wgrad == Wgrad::w3) {
         const size_t shmem = (size_t)2 * 2 * 2 * (OT / 32) * 2 * 64 * 16;
+        if (fold.mode != 0) {
+          if (nob != 1 || fold.mode != (V::two ? 2 : 1)) return (int)DHD_EUNSUPPORTED;
+          return launch_lds<pw_wgrad3_kernel<OT, false, V::two, V::relu, V::two ? 2 : 1>>(grid, block, shmem, shmem, st, a0, a1, acoef, a_bs, b0, b1,
+                                                                                         bcoef, b_bs, partial, c, hw, b, workers, fold.aux,
+                                                                                         fold.mean, fold.rows);
+        }
         return launch_lds<pw_wgrad3_kernel<OT, true, V::two, V::relu>>(grid, block, shmem, shmem, st, a0, a1, acoef, a_bs, b0, b1, bcoef,
-                                                                      b_bs, partial, c, hw, b, workers);
+                                                                      b_bs, partial, c, hw, b, workers, static_cast<const float*>(nullptr),
+                                                                      static_cast<const float*>(nullptr), static_cast<float*>(nullptr));
       } else if (p.wgrad == Wgrad::w6) {
         const size_t shmem = (size_t)2 * 2 * (OT / 32) * 3 * 64 * 16;
         return launch_lds<pw_wgrad6_kernel<OT, true, V::two, V::relu>>(grid, block, shmem, shmem, st, a0, a1, acoef, a_bs, b0, b1, bcoef,
@@ -1708,6 +1925,16 @@ int stage_forward(const Plan& p, const TS* x, const dhd_sfa_weights* w, TO* out,
   return DHD_OK;
 }
 
+// DHD_SFA_BWD_FOLD = 0 | 1 | 2 | 3: the folded backward flow for no layer / layer 2 / layer 1 / both (A/B switch, read once per
+// process).  Default: see LAB_NOTEBOOK R18.
+int bwd_fold_mode() {
+  static const int mode = [] {
+    const char* e = getenv("DHD_SFA_BWD_FOLD");
+    return e != nullptr && e[0] >= '0' && e[0] <= '3' && e[1] == 0 ? e[0] - '0' : kBwdFoldDefault;
+  }();
+  return mode;
+}
+
 // Backward in up to three phases, cut where the two BatchNorm backward passes need their sums (sum g, sum g (y - mu)); `sync`
 // as in stage_forward ((2C + 1) doubles: [sum g][C] | [sum g (y - mu)][C] | count).
 template <class TS, class TO>
@@ -1746,6 +1973,22 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
                        t.dgamma, t.dbeta, t.dbias, b, c, hw, nullptr, sync, reinterpret_cast<const double*>(sv + loc), bias);
   };
   if (sync && !p.fused_stats) return DHD_EUNSUPPORTED;
+  // The folded flow (header comment): per layer, the data gradient first, leaving its prologue's result over g, then the weight
+  // gradient on that one tensor, which also makes the sums pair_sums / blend1_da made in passes of their own.  The worker rows
+  // live where scratch is dead: du's region during phase 1, g2's during phase 2.
+  // The gate is `sync == nullptr`, not the entry point: the phase entry points keep the unfolded flow only because they always pass
+  // a `sync`; a caller that cut the folded flow into phases would find gy, not g, in g2 / g1 between them.
+  int fold = 0;
+  const int fold_workers = wgrad_workers(c);   // the workers launch_wgrad gives the kernels whose rows are read back below
+  if constexpr (std::is_same_v<TS, float>) {
+    const size_t plane = (size_t)b * cs * sizeof(float);
+    // one operand block per launch (all B rows in every worker), and the worker rows fit the dead regions
+    if (p.gemm == Gemm::cu && p.wgrad == Wgrad::w3 && sync == nullptr && wgrad_blocks(c) == 1 && (size_t)fold_workers * 2 * c * sizeof(float) <= plane &&
+        (size_t)(fold_workers + b) * c * sizeof(float) <= plane)
+      fold = bwd_fold_mode();
+  }
+  float* rows1 = reinterpret_cast<float*>(du);   // [worker][2][c]: BatchNorm-1 sums
+  float* rows2 = reinterpret_cast<float*>(g2);   // [worker + sample][c]: du-part of dL/da
 
   if (lo <= 0) {
     // g2 = dL/ds2, BatchNorm-2 sums, go-part of dL/da
@@ -1758,6 +2001,22 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
   if (lo <= 1) {
     if (sync) coef_in(tail2, S.loc2, w->conv2_b);
     DHD_LAUNCH_CHECK();
+  }
+  if (lo <= 1 && (fold & 1)) {
+    if constexpr (std::is_same_v<TS, float>) {
+      // g1 = (W2^T dy2) * [z1 > 0]; dy2 stays in g2
+      rc = launch_gemm(p, GemmCall<TS>{kDgrad2, g2, y2, cs, c, TF(T.tab_g2), sv + S.wp2t, nullptr, mask, nullptr, g1, y1, SF(S.scsh1), CuBlend{}, 0, g2},
+                       b, c, hw, st);
+      if (rc != DHD_OK) return rc;
+      // dW2 = dy2 . z1^T, and the BatchNorm-1 sums of g1 per worker
+      rc = launch_wgrad<TS>(p, kConv2, g2, nullptr, nullptr, cs, y1, nullptr, SF(S.tab1), cs, TF(T.wpart), grads->conv2_w, b, c, hw, st,
+                            WgradFold{1, g1, SF(S.mean1), rows1});
+      if (rc != DHD_OK) return rc;
+      const BnRowsJob j1 = {tail1.gamma, tail1.mean, tail1.rstd, tail1.tab, tail1.dgamma, tail1.dbeta, tail1.dbias, w->training, b, hw};
+      hipLaunchKernelGGL(bn_backward_rows_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, rows1, fold_workers, j1, c);
+      DHD_LAUNCH_CHECK();
+    }
+  } else if (lo <= 1) {
     // dW2 = dy2 . z1^T
     rc = launch_wgrad<TS>(p, kConv2, g2, y2, TF(T.tab_g2), cs, y1, nullptr, SF(S.tab1), cs, TF(T.wpart), grads->conv2_w, b, c, hw, st);
     if (rc != DHD_OK) return rc;
@@ -1772,15 +2031,30 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
   if (hi <= 1) return DHD_OK;
   if (sync) coef_in(tail1, S.loc1, w->conv1_b);
   DHD_LAUNCH_CHECK();
-  // dW1 = dy1 . u^T
-  rc = launch_wgrad<TS>(p, kConv1, g1, y1, TF(T.tab_g1), cs, x, x + cs, SF(S.tab_a), 2 * cs, TF(T.wpart), grads->conv1_w, b, c, hw, st);
-  if (rc != DHD_OK) return rc;
-  // du = W1^T dy1
-  rc = launch_gemm(p, GemmCall<TS>{kDgrad1, g1, y1, cs, c, TF(T.tab_g1), sv + S.wp1t, nullptr, nullptr, nullptr, du}, b, c, hw, st);
-  if (rc != DHD_OK) return rc;
-  hipLaunchKernelGGL(blend1_da_kernel<TS>, planes, dim3(kEwBlock), 0, st, x, du, TF(T.da2), c, hw);
-  hipLaunchKernelGGL(fc_backward_kernel, dim3(b), dim3(kEwBlock), (size_t)(c + r + kEwBlock) * sizeof(float), st, TF(T.da1), TF(T.da2),
-                     SF(S.a1), SF(S.h), w->fc1_w, w->fc2_w, TF(T.dpre2), TF(T.dh), TF(T.ds), c, r);
+  if (fold & 2) {
+    if constexpr (std::is_same_v<TS, float>) {
+      // du = W1^T dy1; dy1 stays in g1
+      rc = launch_gemm(p, GemmCall<TS>{kDgrad1, g1, y1, cs, c, TF(T.tab_g1), sv + S.wp1t, nullptr, nullptr, nullptr, du, nullptr, nullptr, CuBlend{}, 0, g1},
+                       b, c, hw, st);
+      if (rc != DHD_OK) return rc;
+      // dW1 = dy1 . u^T, and the du-part of dL/da per (worker, sample)
+      rc = launch_wgrad<TS>(p, kConv1, g1, nullptr, nullptr, cs, x, x + cs, SF(S.tab_a), 2 * cs, TF(T.wpart), grads->conv1_w, b, c, hw, st,
+                            WgradFold{2, du, nullptr, rows2});
+      if (rc != DHD_OK) return rc;
+      hipLaunchKernelGGL(fc_backward_kernel, dim3(b), dim3(kEwBlock), (size_t)(c + r + kEwBlock) * sizeof(float), st, TF(T.da1), rows2,
+                         SF(S.a1), SF(S.h), w->fc1_w, w->fc2_w, TF(T.dpre2), TF(T.dh), TF(T.ds), c, r, fold_workers, (hw + 31) / 32);
+    }
+  } else {
+    // dW1 = dy1 . u^T
+    rc = launch_wgrad<TS>(p, kConv1, g1, y1, TF(T.tab_g1), cs, x, x + cs, SF(S.tab_a), 2 * cs, TF(T.wpart), grads->conv1_w, b, c, hw, st);
+    if (rc != DHD_OK) return rc;
+    // du = W1^T dy1
+    rc = launch_gemm(p, GemmCall<TS>{kDgrad1, g1, y1, cs, c, TF(T.tab_g1), sv + S.wp1t, nullptr, nullptr, nullptr, du}, b, c, hw, st);
+    if (rc != DHD_OK) return rc;
+    hipLaunchKernelGGL(blend1_da_kernel<TS>, planes, dim3(kEwBlock), 0, st, x, du, TF(T.da2), c, hw);
+    hipLaunchKernelGGL(fc_backward_kernel, dim3(b), dim3(kEwBlock), (size_t)(c + r + kEwBlock) * sizeof(float), st, TF(T.da1), TF(T.da2),
+                       SF(S.a1), SF(S.h), w->fc1_w, w->fc2_w, TF(T.dpre2), TF(T.dh), TF(T.ds), c, r, 0, 0);
+  }
   const int n_fc = r * 2 * c + c * r + r + c;
   const FcGradJob fcj = {TF(T.dpre2), TF(T.dh), SF(S.h), SF(S.s), grads->fc1_w, grads->fc1_b, grads->fc2_w, grads->fc2_b, b, r};
   const int fc_rows = dhd_cdiv(dhd_cdiv(n_fc, kEwBlock), kPlaneChunks);
