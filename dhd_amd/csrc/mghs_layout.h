@@ -83,6 +83,21 @@ __host__ __device__ inline int pt_index(const Layout& L, int bn, int d, int h, i
 #endif
 }
 
+// Two roles in one launch (mghs_pool.hip, DHD_MGHS_BY_GRID): a streaming role and a point role share the launch in GROUPS of 8
+// consecutive workgroups (one per XCD: the point bodies place their work by blockIdx & 7).  Of the n = n_stream + n_point groups,
+// group g is a point group where floor(g' * n_point / n) steps from g' = g to g + 1 -- the point groups lie evenly among the
+// stream groups, so both kinds are resident from the start of the launch to its end -- and a stream group otherwise; `index`
+// counts the groups of the same role before it.  Either count may be 0 (n > 0).
+struct RoleSlot { int point, index; };
+__host__ __device__ inline RoleSlot role_of_group(int g, int n_stream, int n_point) {
+  const long long n = (long long)n_stream + n_point;
+  const int before = (int)((long long)g * n_point / n), upto = (int)((long long)(g + 1) * n_point / n);
+  RoleSlot r;
+  r.point = upto > before ? 1 : 0;
+  r.index = r.point ? before : g - before;
+  return r;
+}
+
 // Fills *L from the description; with `ws` also carves the device pointers and checks the sizes.  state_bytes /
 // scratch_bytes (optional) receive the sizes needed.
 inline int make_layout(const dhd_mghs_desc* d, const dhd_mghs_workspace* ws, Layout* L, size_t* state_bytes = nullptr,

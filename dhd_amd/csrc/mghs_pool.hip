@@ -94,17 +94,18 @@ __device__ __forceinline__ int channels_per_pass(int nnz) {
 // sum per entry slot, as mghs_pixel_bwd now does.  Every voxel boundary then needs a cross-slot reduction (8 lane
 // exchanges) where this form needs none, and voxels are short (8-17 entries): DHD-S 0.394 -> 0.440 ms per step, DHD-L
 // geometry 1.09 -> 1.28 ms.)
-template <int J>
+// GatherStep<J, END, N>: positions [J, END) of the batch with N (a power of two) registers for the loaded rows
+template <int J, int END, int N>
 struct GatherStep {
-  static __device__ __forceinline__ void load(float (&f)[DHD_WAVE], __amdgpu_buffer_rsrc_t feat_rsrc, int lane4, int pix,
+  static __device__ __forceinline__ void load(float (&f)[N], __amdgpu_buffer_rsrc_t feat_rsrc, int lane4, int pix,
                                               int jmax) {
     if ((J & 7) == 0 && J > jmax) return;  // wave-uniform early exit, checked every 8 positions
     // buffer load: per-lane byte offset in a VGPR (constant), row offset (pixel * 256 B) in an SGPR:
     // one v_readlane + one s_lshl + one buffer_load per entry, no vector address arithmetic
-    f[J] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(feat_rsrc, lane4, lane_i(pix, J) << 8, 0));
-    GatherStep<J + 1>::load(f, feat_rsrc, lane4, pix, jmax);
+    f[J & (N - 1)] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(feat_rsrc, lane4, lane_i(pix, J) << 8, 0));
+    GatherStep<J + 1, END, N>::load(f, feat_rsrc, lane4, pix, jmax);
   }
-  static __device__ __forceinline__ void run(const float (&f)[DHD_WAVE], unsigned long long firsts, int term, int slot,
+  static __device__ __forceinline__ void run(const float (&f)[N], unsigned long long firsts, int term, int slot,
                                              float dv, float* vrow, int scratch_row, int jmax, int& cur, float& acc) {
     if ((J & 7) == 0 && J > jmax) return;
     if ((firsts >> J) & 1ull) {
@@ -112,24 +113,31 @@ struct GatherStep {
       cur = rfl((J == term) ? scratch_row : lane_i(slot, J));
       acc = 0.f;
     }
-    acc = fmaf(lane_f(dv, J), f[J], acc);
-    GatherStep<J + 1>::run(f, firsts, term, slot, dv, vrow, scratch_row, jmax, cur, acc);
+    acc = fmaf(lane_f(dv, J), f[J & (N - 1)], acc);
+    GatherStep<J + 1, END, N>::run(f, firsts, term, slot, dv, vrow, scratch_row, jmax, cur, acc);
   }
 };
-template <>
-struct GatherStep<DHD_WAVE> {
-  static __device__ __forceinline__ void load(float (&)[DHD_WAVE], __amdgpu_buffer_rsrc_t, int, int, int) {}
-  static __device__ __forceinline__ void run(const float (&)[DHD_WAVE], unsigned long long, int, int, float, float*, int, int,
+template <int END, int N>
+struct GatherStep<END, END, N> {
+  static __device__ __forceinline__ void load(float (&)[N], __amdgpu_buffer_rsrc_t, int, int, int) {}
+  static __device__ __forceinline__ void run(const float (&)[N], unsigned long long, int, int, float, float*, int, int,
                                              int&, float&) {}
 };
 
-// BANDS_ONLY: the entries of the full-height grid 0 (the first offset[vox_base[1]] of the list) are left to mghs_col_sums.
-template <bool BANDS_ONLY>
+// PART: which entries of the list.  kBandsOnly: the entries of the full-height grid 0 (the first offset[vox_base[1]] of the list)
+// are left to mghs_col_sums or to a kGrid0Only gather in another launch; kGrid0Only: those entries alone -- the list ends for
+// this body where grid 0's entries end, so the wave that owns grid 0's last voxel stops there.  A voxel is summed by one wave in
+// entry order whichever PART it is reached through: the sums are the same bytes.
+// `block` stands for blockIdx.x of a launch of kBlock-thread workgroups, `wib` for the wave inside such a workgroup (a wider
+// workgroup of a merged kernel serves several).  HALF: the rows of a batch are loaded and summed 32 at a time, in the same order
+// (32 registers fewer: the merged kernel must not take the streaming role's occupancy, see mghs_fwd_bands_g0sums).
+enum { kAllGrids = 0, kBandsOnly = 1, kGrid0Only = 2 };
+template <int PART, bool HALF = false>
 __device__ __forceinline__ void gather_sums_body(const Layout& L, const float* __restrict__ depth, const float* __restrict__ feat,
-                                                 const int block) {
+                                                 const int block, const int wib) {
   const int lane = threadIdx.x & 63;
-  const int T0 = BANDS_ONLY ? L.offset[L.vox_base[1]] : 0;
-  const int T = L.offset[L.V];  // total entries (device-side value, scalar load)
+  const int T0 = PART == kBandsOnly ? L.offset[L.vox_base[1]] : 0;
+  const int T = PART == kGrid0Only ? L.offset[L.vox_base[1]] : L.offset[L.V];  // end of the entries (device-side value, scalar load)
   // everything that steers control flow is forced into SGPRs: the compiler cannot see that
   // threadIdx.x >> 6 is wave-uniform and would otherwise predicate every branch through EXEC
   // XCD x (workgroups x, x+8, ...) takes the x-th eighth of the entries actually present: entries are
@@ -137,7 +145,7 @@ __device__ __forceinline__ void gather_sums_body(const Layout& L, const float* _
   const int per_xcd = ((T - T0 + kBlock - 1) / kBlock + 7) >> 3;
   if ((block >> 3) >= per_xcd) return;
   const int wg = (block & 7) * per_xcd + (block >> 3);
-  const int a = rfl(T0 + (wg * (kBlock / DHD_WAVE) + (threadIdx.x >> 6)) * DHD_WAVE);
+  const int a = rfl(T0 + (wg * (kBlock / DHD_WAVE) + wib) * DHD_WAVE);
   if (a >= T) return;
   const int b = min(T, a + DHD_WAVE);
   const __amdgpu_buffer_rsrc_t feat_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -194,9 +202,18 @@ __device__ __forceinline__ void gather_sums_body(const Layout& L, const float* _
     }
     if (lo < nb) {
       const int jmax = last ? term : DHD_WAVE - 1;
-      float f[DHD_WAVE];
-      GatherStep<0>::load(f, feat_rsrc, lane4, pix, jmax);
-      GatherStep<0>::run(f, firsts, term, slot, dv, vrow, scratch_row, jmax, cur, acc);
+      if (HALF) {
+        constexpr int H = DHD_WAVE / 2;
+        float f[H];
+        GatherStep<0, H, H>::load(f, feat_rsrc, lane4, pix, jmax);
+        GatherStep<0, H, H>::run(f, firsts, term, slot, dv, vrow, scratch_row, jmax, cur, acc);
+        GatherStep<H, DHD_WAVE, H>::load(f, feat_rsrc, lane4, pix, jmax);
+        GatherStep<H, DHD_WAVE, H>::run(f, firsts, term, slot, dv, vrow, scratch_row, jmax, cur, acc);
+      } else {
+        float f[DHD_WAVE];
+        GatherStep<0, DHD_WAVE, DHD_WAVE>::load(f, feat_rsrc, lane4, pix, jmax);
+        GatherStep<0, DHD_WAVE, DHD_WAVE>::run(f, firsts, term, slot, dv, vrow, scratch_row, jmax, cur, acc);
+      }
     }
     if (last) { cur = rfl(scratch_row); break; }
     dv_n = 0.f;
@@ -205,10 +222,10 @@ __device__ __forceinline__ void gather_sums_body(const Layout& L, const float* _
   vrow[(size_t)cur * kTileC] = acc;
 }
 
-template <bool BANDS_ONLY>
+template <int PART>
 __global__ __launch_bounds__(kBlock) void mghs_gather_sums(Layout L, const float* __restrict__ depth,
                                                             const float* __restrict__ feat) {
-  gather_sums_body<BANDS_ONLY>(L, depth, feat, (int)blockIdx.x);
+  gather_sums_body<PART>(L, depth, feat, (int)blockIdx.x, (int)(threadIdx.x >> 6));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -311,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void mghs_sums_cols_bands(Layout L, const f
     const int cg = kc * period + r;
     if (cg < n_col_groups) col_sums_body<FH>(L, depth, feat, (cg << 3) | x);
   } else if (period < n_gather_groups) {
-    gather_sums_body<true>(L, depth, feat, (period << 3) | x);
+    gather_sums_body<kBandsOnly>(L, depth, feat, (period << 3) | x, (int)(threadIdx.x >> 6));
   }
 }
 
@@ -347,20 +364,21 @@ template <class T> __device__ __forceinline__ f32x4 pack_vox(const float* f) {
 }
 template <class T> __device__ __forceinline__ void unpack_vox(f32x4 v, float* f) { widen16<T>(__builtin_bit_cast(raw16<T>, v), f); }
 
-// OP = 1: the same code instantiated once more for the single-grid operator (dhd_bev_pool_v2_fused_*), so that its launches are
-// their own rows in a kernel profile instead of being averaged into the hot path's.
-template <class T, int OP = 0>
-__global__ __launch_bounds__(kStreamBlock) void mghs_stream_fwd(Layout L, OutPtrs out, int split) {
+// `wg` stands for blockIdx.x of a launch over the segments [seg_lo, seg_hi) x `split` parts (the merged kernel numbers the
+// workgroups of its streaming role itself).
+template <class T>
+__device__ __forceinline__ void stream_fwd_body(const Layout& L, const OutPtrs& out, const int split, const int wg, const int seg_lo,
+                                                const int seg_hi) {
   constexpr int VPL = kVec16<T>;                // voxels per lane and store: 4 (float32) or 8 (half types)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* table = reinterpret_cast<float*>(smem);
   unsigned short* slot_of = reinterpret_cast<unsigned short*>(smem + (size_t)kTableFloats * 4);
   int* ctl = reinterpret_cast<int*>(smem + (size_t)kTableFloats * 4 + (size_t)kSegMaxVox * 2);
 
-  const int seg = blockIdx.x / split, pw = kTileC / split;
-  const int c_begin = (blockIdx.x % split) * pw, c_end = c_begin + pw;
+  const int seg = seg_lo + wg / split, pw = kTileC / split;
+  const int c_begin = (wg % split) * pw, c_end = c_begin + pw;
   Segment sg;
-  if (!decode_segment(L, seg, &sg)) return;
+  if (seg >= seg_hi || !decode_segment(L, seg, &sg)) return;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   if (t == 0) ctl[0] = L.nzoff[sg.v0];
   if (t == 1) ctl[1] = L.nzoff[sg.v0 + sg.nvox];
@@ -420,6 +438,54 @@ __global__ __launch_bounds__(kStreamBlock) void mghs_stream_fwd(Layout L, OutPtr
       i += r_step;
       if (i >= nvec) { i -= nvec; ++cc; }
     }
+  }
+}
+
+// OP = 1: the same code instantiated once more for the single-grid operator (dhd_bev_pool_v2_fused_*), so that its launches are
+// their own rows in a kernel profile instead of being averaged into the hot path's; OP = 2: the launch over grid 0's segments
+// alone (forward by grid, below), a row of its own likewise.
+template <class T, int OP = 0>
+__global__ __launch_bounds__(kStreamBlock) void mghs_stream_fwd(Layout L, OutPtrs out, int split, int seg_lo, int seg_hi) {
+  stream_fwd_body<T>(L, out, split, (int)blockIdx.x, seg_lo, seg_hi);
+}
+
+// ---------------------------------------------------------------------------------------
+// Forward by grid (DHD_MGHS_BY_GRID): grid 0's point sums under the band grids' writer.  The writer is HBM-bound, the gather
+// waits on L2 with HBM nearly idle, and the grids' outputs do not depend on one another: grid 0 holds 80 % of the entries but
+// 1/17 of the output bytes, the band grids the rest.  Launch order on the one stream is the only dependency; no flags, no
+// second stream.
+//   1. mghs_gather_sums<kBandsOnly>  point sums of the band grids
+//   2. mghs_fwd_bands_g0sums         writer of the band grids' segments || sorted gather of grid 0's entries (disjoint vsum slots)
+//   3. mghs_stream_fwd<T, 2>         writer of grid 0's segments
+// The merged kernel has the writer's workgroups (kStreamBlock threads, kStreamLds); a workgroup of the point role serves
+// kStreamBlock / kBlock workgroups' worth of the gather body.  The roles alternate in groups of 8 workgroups (role_of_group,
+// mghs_layout.h).  Registers (-Rpass-analysis=kernel-resource-usage): the float32 writer alone has 61 VGPRs = four workgroups
+// per CU; the gather with 64 rows in flight has 84, which would leave two, so the gather role takes its rows 32 at a time
+// (HALF) and the kernel is held to 64 registers by its launch bounds: 61 VGPRs (57 for the half types), no scratch.
+// Kept for the sorted gather only; the column form of grid 0 (fH = 32) under the writer and the backward by grid (reader of
+// one band || the pixels of another) were built, measured slower than today's flow and removed: docs/LAB_NOTEBOOK.md R19.
+// -DDHD_MERGED_GATHER_HALF=0 -DDHD_MERGED_WAVES=5: 64 rows in flight at 84 registers, for A/B builds.
+// ---------------------------------------------------------------------------------------
+#ifndef DHD_MERGED_GATHER_HALF
+#define DHD_MERGED_GATHER_HALF 1
+#endif
+#ifndef DHD_MERGED_WAVES
+#define DHD_MERGED_WAVES 8
+#endif
+constexpr int kPointPerStream = kStreamBlock / kBlock;   // kBlock-sized point workgroups served by one merged workgroup
+
+template <class T>
+__global__ __launch_bounds__(kStreamBlock, DHD_MERGED_WAVES) void mghs_fwd_bands_g0sums(Layout L, OutPtrs out, int split,
+                                                                                        const float* __restrict__ depth,
+                                                                                        const float* __restrict__ feat,
+                                                                                        int n_stream_groups, int n_point_groups) {
+  const int grp = rfl((int)(blockIdx.x >> 3)), x = (int)(blockIdx.x & 7);
+  const RoleSlot r = role_of_group(grp, n_stream_groups, n_point_groups);
+  if (r.point) {
+    const int block = ((kPointPerStream * r.index + (int)(threadIdx.x / kBlock)) << 3) | x;
+    gather_sums_body<kGrid0Only, DHD_MERGED_GATHER_HALF != 0>(L, depth, feat, block, (int)(threadIdx.x % kBlock) >> 6);
+  } else {
+    stream_fwd_body<T>(L, out, split, (r.index << 3) | x, L.seg_base[1], L.n_segs);
   }
 }
 
@@ -849,12 +915,12 @@ int launch_stream_fwd(const Layout& L, const OutPtrs& o, int split, hipStream_t 
   if (!L.compact || L.n_segs <= 0) return DHD_EINVAL;
   if (op) {
     if (o.dtype != DHD_F32) return DHD_EUNSUPPORTED;
-    hipLaunchKernelGGL((mghs_stream_fwd<float, 1>), dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split);
+    hipLaunchKernelGGL((mghs_stream_fwd<float, 1>), dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split, 0, L.n_segs);
     DHD_LAUNCH_CHECK();
     return DHD_OK;
   }
   return with_dtype<NativeHalf>(o.dtype, [&](auto* t) {
-    hipLaunchKernelGGL(mghs_stream_fwd<std::remove_pointer_t<decltype(t)>>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split);
+    hipLaunchKernelGGL(mghs_stream_fwd<std::remove_pointer_t<decltype(t)>>, dim3(L.n_segs * split), dim3(kStreamBlock), kStreamLds, st, L, o, split, 0, L.n_segs);
     DHD_LAUNCH_CHECK();
     return DHD_OK;
   });
@@ -913,11 +979,11 @@ int dhd_mghs_forward_gather(const dhd_mghs_desc* desc, const float* depth, const
       hipLaunchKernelGGL(mghs_sums_cols_bands<32>, dim3(periods * (kc + 1) * 8), dim3(kBlock), 0, st, L, depth, feat_nhwc, ncg, ngg, kc);
     } else {
       hipLaunchKernelGGL(mghs_col_sums<32>, grid, dim3(kBlock), 0, st, L, depth, feat_nhwc);
-      hipLaunchKernelGGL(mghs_gather_sums<true>, dim3(n_gather), dim3(kBlock), 0, st, L, depth, feat_nhwc);
+      hipLaunchKernelGGL(mghs_gather_sums<kBandsOnly>, dim3(n_gather), dim3(kBlock), 0, st, L, depth, feat_nhwc);
     }
   } else {
     // 2P is an upper bound of the entry count; waves past the real count exit at once
-    hipLaunchKernelGGL(mghs_gather_sums<false>, dim3(dhd_cdiv(2L * L.P, 8 * kBlock) * 8), dim3(kBlock), 0, st, L, depth, feat_nhwc);
+    hipLaunchKernelGGL(mghs_gather_sums<kAllGrids>, dim3(dhd_cdiv(2L * L.P, 8 * kBlock) * 8), dim3(kBlock), 0, st, L, depth, feat_nhwc);
   }
   DHD_LAUNCH_CHECK();
   return DHD_OK;
@@ -958,19 +1024,72 @@ int dhd_mghs_forward_stream_views(const dhd_mghs_desc* desc, const float* depth,
   return forward_stream_impl(desc, depth, feat_nhwc, nullptr, out, workspace, stream);
 }
 
+// DHD_MGHS_BY_GRID = 0 / 1 / 2 / 3: none / forward / backward / both directions by grid (see mghs_fwd_bands_g0sums); read once
+// per process.  Only the forward with the sorted gather of grid 0 is by grid today: the backward lost (bit 2 is accepted and
+// changes nothing) and so did the forward in column mode, which keeps today's flow under every value.  Unset: forward by grid.
+enum { kByGridForward = 1, kByGridBackward = 2 };
+static int by_grid(const Layout& L) {
+  static const int env = [] {
+    const char* s = getenv("DHD_MGHS_BY_GRID");
+    return s && *s ? atoi(s) & (kByGridForward | kByGridBackward) : kByGridForward;
+  }();
+  return L.compact && L.G > 1 && !L.columns ? env : 0;
+}
+
+static int forward_by_grid(const Layout& L, const float* depth, const float* feat_nhwc, const OutPtrs& o, hipStream_t st) {
+  const int split = o.dtype == DHD_F32 ? stream_split(L) : 2;   // as forward_stream_impl
+  // 1. the band grids' point sums: at most one entry per point
+  const int n_gather = dhd_cdiv((long)L.P, 8 * kBlock) * 8;
+  hipLaunchKernelGGL(mghs_gather_sums<kBandsOnly>, dim3(n_gather), dim3(kBlock), 0, st, L, depth, feat_nhwc);
+  DHD_LAUNCH_CHECK();
+  // 2. their writer || grid 0's point sums (at most one entry per point as well), in groups of 8 workgroups; never 0 blocks
+  const int n_stream = dhd_cdiv((long)(L.n_segs - L.seg_base[1]) * split, 8L);
+  const int n_point = dhd_cdiv((long)(n_gather / 8), (long)kPointPerStream);
+  if (n_stream + n_point > 0) {
+    int rc = with_dtype<NativeHalf>(o.dtype, [&](auto* t) {
+      hipLaunchKernelGGL(mghs_fwd_bands_g0sums<std::remove_pointer_t<decltype(t)>>, dim3((n_stream + n_point) * 8), dim3(kStreamBlock), kStreamLds,
+                         st, L, o, split, depth, feat_nhwc, n_stream, n_point);
+      DHD_LAUNCH_CHECK();
+      return DHD_OK;
+    });
+    if (rc) return rc;
+  }
+  // 3. grid 0's writer
+  if (L.seg_base[1] <= 0) return DHD_OK;
+  return with_dtype<NativeHalf>(o.dtype, [&](auto* t) {   // (2 / 8 / 16 parts for this launch alone: no faster, R19)
+    hipLaunchKernelGGL((mghs_stream_fwd<std::remove_pointer_t<decltype(t)>, 2>), dim3(L.seg_base[1] * split), dim3(kStreamBlock), kStreamLds, st,
+                       L, o, split, 0, L.seg_base[1]);
+    DHD_LAUNCH_CHECK();
+    return DHD_OK;
+  });
+}
+
+static int forward_impl(const dhd_mghs_desc* desc, const float* depth, const float* feat_nhwc, float* const out[DHD_MAX_GRIDS],
+                        const dhd_tensor_view* views, const dhd_mghs_workspace* workspace, void* stream) {
+  Layout L;
+  int rc = make_layout(desc, workspace, &L);
+  if (rc) return rc;
+  if (by_grid(L) & kByGridForward) {
+    if (!workspace || !depth || !feat_nhwc || (!out && !views)) return DHD_EINVAL;
+    if (!dhd_aligned(16, feat_nhwc)) return DHD_EINVAL;
+    OutPtrs o;
+    if ((rc = make_views<OutPtrs, float>(L, out, views, &o))) return rc;
+    return forward_by_grid(L, depth, feat_nhwc, o, dhd_stream(stream));
+  }
+  // the phase entry points keep this flow under every switch value (bench.py --full times the writer through them)
+  if ((rc = dhd_mghs_forward_gather(desc, depth, feat_nhwc, workspace, stream))) return rc;
+  return forward_stream_impl(desc, depth, feat_nhwc, out, views, workspace, stream);
+}
+
 int dhd_mghs_forward(const dhd_mghs_desc* desc, const float* depth, const float* feat_nhwc,
                      float* const out[DHD_MAX_GRIDS], const dhd_mghs_workspace* workspace, void* stream) {
-  int rc = dhd_mghs_forward_gather(desc, depth, feat_nhwc, workspace, stream);
-  if (rc) return rc;
-  return forward_stream_impl(desc, depth, feat_nhwc, out, nullptr, workspace, stream);
+  return forward_impl(desc, depth, feat_nhwc, out, nullptr, workspace, stream);
 }
 
 int dhd_mghs_forward_views(const dhd_mghs_desc* desc, const float* depth, const float* feat_nhwc,
                            const dhd_tensor_view out[DHD_MAX_GRIDS], const dhd_mghs_workspace* workspace, void* stream) {
   if (!out) return DHD_EINVAL;
-  int rc = dhd_mghs_forward_gather(desc, depth, feat_nhwc, workspace, stream);
-  if (rc) return rc;
-  return forward_stream_impl(desc, depth, feat_nhwc, nullptr, out, workspace, stream);
+  return forward_impl(desc, depth, feat_nhwc, nullptr, out, workspace, stream);
 }
 
 static int backward_impl(const dhd_mghs_desc* desc, const float* depth, const float* feat_nhwc,
