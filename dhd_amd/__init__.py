@@ -16,7 +16,7 @@ from .ema import ModelEMA, MEGVIIEMAHook, SyncbnControlHook, SequentialControlHo
 from .config import Config  # noqa: F401
 from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noqa: F401
 from .amp_weights import HalfWeightCache  # noqa: F401
-from .occ_head import occ_head_infer  # noqa: F401
+from .occ_head import occ_head_infer, occ_head_train  # noqa: F401
 from .deform_conv import deform_conv_infer, deform_conv_infer_supported  # noqa: F401
 from . import window_attn  # noqa: F401  (the module, callable as its function window_attn)
 from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
@@ -113,6 +113,21 @@ def fused_swin_ffn_training_wide(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, SwinBlock)]
     for m in switched:
         m.fused_ffn_train_wide = bool(on)
+    return switched
+
+
+def fused_occ_head_training(model, on=True):
+    """Sets `fused_train` on every occupancy head (`predictor`) of `model` and returns the heads it switched.  With it the head's
+    predicter -- Linear, Softplus, Linear per BEV cell -- runs as `occ_head_train`, the fused forward that writes float32 logits
+    and its recompute HIP backward, in train and eval mode, with or without grad, wherever the operator has the shape (256
+    channels, 512 hidden units, 16 x 18 logits, a GPU tensor) and the measurement routed that dtype and layout to it
+    (occ_head.ROUTED_TRAIN); every other call keeps today's path bit for bit.  It is a switch of its own: fused_inference and
+    `predict_occ` are untouched and it sets none of the other switches.  Within the layer's bar of the module formulation, not
+    bit-identical; under autocast the logits come out in float32 where the module formulation hands the loss a half tensor to cast."""
+    from .detector import predictor
+    switched = [m for m in model.modules() if isinstance(m, predictor)]
+    for m in switched:
+        m.fused_train = bool(on)
     return switched
 
 

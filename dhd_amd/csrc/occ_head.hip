@@ -391,3 +391,6 @@ int dhd_occ_head_infer(const void* x, int x_dtype, int layout, const dhd_occ_hea
 }
 
 }  // extern "C"
+
+// the training half: the recompute backward and its dhdo_* entry points (the forward in training is dhd_occ_head_infer itself)
+#include "occ_head_train.h"

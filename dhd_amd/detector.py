@@ -19,6 +19,8 @@ reference imports from un-vendored packages are restated from their published de
   predictor         models/dense_heads/occ_head.py:32-153 (+ losses/semkitti_loss.py:136-226)
   DHD               models/detectors/DHD_model.py:10-241
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -498,8 +500,26 @@ class predictor(nn.Module):
         self.loss_occ = CrossEntropyLoss(**loss_cfg)
         self.weight_ce, self.weight_geo, self.weight_sem = weight_ce, weight_geo, weight_sem
 
+    # Opt-in (dhd_amd.fused_occ_head_training, or DHD_OCC_HEAD_TRAIN=1 in the environment so that a whole training step can be
+    # switched from outside): forward sends final_conv's output to occ_head.occ_head_train -- the fused forward writing float32
+    # logits and its recompute HIP backward -- in train and eval mode, with or without grad, where the operator has the shape and
+    # the measurement routed that dtype and layout to it (occ_head.ROUTED_TRAIN).  Off, or anywhere else: today's path, bit for bit.
+    fused_train = bool(os.environ.get('DHD_OCC_HEAD_TRAIN'))
+
+    def _train_applies(self, x):
+        """True when forward runs occ_head_train on final_conv's output `x`."""
+        if not (self.fused_train and self.use_predicter and torch.is_tensor(x) and x.is_cuda):
+            return False
+        from . import occ_head
+        return occ_head.train_routed(x, self.predicter[0].weight, self.predicter[2].weight, self.Dz)
+
     def forward(self, img_feats):
-        x = self.final_conv(img_feats).permute(0, 3, 2, 1)  # (B, Dx, Dy, C)
+        x = self.final_conv(img_feats)
+        if self._train_applies(x):
+            from . import occ_head
+            lin1, lin2 = self.predicter[0], self.predicter[2]
+            return occ_head.occ_head_train(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, self.Dz)  # (B, Dx, Dy, Dz, classes) float32
+        x = x.permute(0, 3, 2, 1)  # (B, Dx, Dy, C)
         if self.use_predicter:
             b, dx, dy = x.shape[:3]
             x = self.predicter(x).view(b, dx, dy, self.Dz, self.num_classes)
