@@ -17,7 +17,8 @@ from .config import Config  # noqa: F401
 from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noqa: F401
 from .amp_weights import HalfWeightCache  # noqa: F401
 from .occ_head import occ_head_infer, occ_head_train  # noqa: F401
-from .deform_conv import deform_conv_infer, deform_conv_infer_supported  # noqa: F401
+from . import deform_conv  # noqa: F401  (the module, callable as its function deform_conv)
+from .deform_conv import deform_conv_infer, deform_conv_infer_supported, deform_conv_train_supported  # noqa: F401
 from . import window_attn  # noqa: F401  (the module, callable as its function window_attn)
 from .window_attn import window_attn_infer, window_attn_infer_supported, window_attn_supported  # noqa: F401
 from .swin_glue import layer_norm_rows, window_reverse_add, swin_glue_supported  # noqa: F401
@@ -126,6 +127,21 @@ def fused_occ_head_training(model, on=True):
     bit-identical; under autocast the logits come out in float32 where the module formulation hands the loss a half tensor to cast."""
     from .detector import predictor
     switched = [m for m in model.modules() if isinstance(m, predictor)]
+    for m in switched:
+        m.fused_train = bool(on)
+    return switched
+
+
+def fused_dcn_training(model, on=True):
+    """Sets `fused_train` on every `DCN` of `model` and returns the modules it switched.  With it the deformable convolution of the
+    HeightNet / DepthNet stacks runs as `deform_conv` -- the fused forward of the inference operator and its HIP backward, which
+    neither keeps the column matrix nor writes its gradient -- in train and eval mode, with or without grad, wherever the operator
+    has the shape (3 x 3, C / groups and O / groups multiples of 8 up to 128, a map of at most 853 cells, a GPU tensor) and the
+    measurement routed that dtype and layout to it (deform_conv.ROUTED_TRAIN); every other call keeps today's path bit for bit.  It
+    is a switch of its own: fused_inference is untouched and it sets none of the other switches.  Within the layer's bar of
+    today's path, not bit-identical."""
+    from .depthnet import DCN
+    switched = [m for m in model.modules() if isinstance(m, DCN)]
     for m in switched:
         m.fused_train = bool(on)
     return switched

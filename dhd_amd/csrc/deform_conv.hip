@@ -109,6 +109,69 @@ __device__ __forceinline__ void load_corners(const T* __restrict__ xg, const int
   }
 }
 
+// 16 bytes of a run of consecutive elements, as loaded, as float32 (4 values, or 8 of a half type)
+template <class T>
+__device__ __forceinline__ void widen_quad(u32x4 q, float* xv) {
+  if constexpr (std::is_same_v<T, float>) {
+#pragma unroll
+    for (int z = 0; z < 4; ++z) xv[z] = __uint_as_float(q[z]);
+  } else {
+#pragma unroll
+    for (int z = 0; z < 4; ++z) {
+      const f32x2 p = Pair<T>::widen(q[z]);
+      xv[2 * z] = p.x;
+      xv[2 * z + 1] = p.y;
+    }
+  }
+}
+
+// a run of 8 consecutive elements, as loaded, as float32
+template <class T>
+__device__ __forceinline__ void widen_run(const u32x4 (&q)[kRun<T>], float* xv) {
+#pragma unroll
+  for (int e = 0; e < kRun<T>; ++e) widen_quad<T>(q[e], xv + 4 * e);
+}
+
+// the 8 values of corner i of a lane's run as float32; a corner outside the image gives zeros
+template <class T>
+__device__ __forceinline__ void corner_values(const Corners<T>& cr, int i, float* xv) {
+  const bool ok = (cr.valid >> i) & 1;
+#pragma unroll
+  for (int e = 0; e < kRun<T>; ++e) {
+    u32x4 q = cr.q[i][e];
+#pragma unroll
+    for (int z = 0; z < 4; ++z) q[z] = ok ? q[z] : 0u;
+    widen_quad<T>(q, xv + 4 * e);
+  }
+}
+
+// 8 consecutive-k float32 values as the lane's MFMA operand: rounded once to a half type, or cut into bf16 high + residual
+template <class T>
+__device__ __forceinline__ void operand_of(const float* v, u32x4 (&xf)[kParts<T>]) {
+#pragma unroll
+  for (int jp = 0; jp < 4; ++jp) {
+    if constexpr (kParts<T> == 2) {
+      unsigned hi, mid;
+      split2_hm(v[2 * jp], v[2 * jp + 1], hi, mid);
+      xf[0][jp] = hi;
+      xf[kParts<T> - 1][jp] = mid;
+    } else {
+      xf[0][jp] = Pair<T>::narrow(f32x2{v[2 * jp], v[2 * jp + 1]});
+    }
+  }
+}
+
+// acc += A B with both operands in kParts<T> parts: three products of a two-part split, smallest terms first, or one product
+template <class T>
+__device__ __forceinline__ f32x16 mfma_parts(const u32x4 (&a)[kParts<T>], const u32x4 (&b)[kParts<T>], f32x16 acc) {
+  constexpr int P = kParts<T>;
+  if constexpr (P == 2) {
+    acc = mfma16<T>(a[P - 1], b[0], acc);
+    acc = mfma16<T>(a[0], b[P - 1], acc);
+  }
+  return mfma16<T>(a[0], b[0], acc);
+}
+
 // the 8 sampled values of the lane, deform_im2col's chain: v = 0, then fmaf(weight, corner, v) over the valid corners in the
 // order 00, 01, 10, 11.  A corner outside the image enters as fmaf(0, 0, v) = v.
 template <class T>
@@ -117,25 +180,8 @@ __device__ __forceinline__ void blend(const Corners<T>& cr, float* v) {
   for (int j = 0; j < 8; ++j) v[j] = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const bool ok = (cr.valid >> i) & 1;
     float xv[8];
-#pragma unroll
-    for (int e = 0; e < kRun<T>; ++e) {
-      u32x4 q = cr.q[i][e];
-#pragma unroll
-      for (int z = 0; z < 4; ++z) q[z] = ok ? q[z] : 0u;
-      if constexpr (std::is_same_v<T, float>) {
-#pragma unroll
-        for (int z = 0; z < 4; ++z) xv[4 * e + z] = __uint_as_float(q[z]);
-      } else {
-#pragma unroll
-        for (int z = 0; z < 4; ++z) {
-          const f32x2 p = Pair<T>::widen(q[z]);
-          xv[2 * z] = p.x;
-          xv[2 * z + 1] = p.y;
-        }
-      }
-    }
+    corner_values<T>(cr, i, xv);
     const float wi = cr.wt[i];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = fmaf(wi, xv[j], v[j]);
@@ -143,6 +189,48 @@ __device__ __forceinline__ void blend(const Corners<T>& cr, float* v) {
   if (!(cr.valid & 16)) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = 0.f;
+  }
+}
+
+// The accumulator tiles of a wave -- register e of tile m: channel 32 m + 8 (e >> 2) + 4 hh + (e & 3) of group g (n_g channels per
+// group, n_all in all), pixel p0 + px of image b -- stored into a (B, n_all, hw) tensor: channels_last as 4 consecutive channels
+// per lane, NCHW with consecutive pixels on consecutive lanes.
+template <class T, bool OUT_NHWC, int MT>
+__device__ __forceinline__ void store_tiles(const f32x16 (&acc)[MT], T* __restrict__ out, int b, int hw, int p0, int px, bool live, int hh,
+                                            int g, int n_g, int n_all) {
+  if constexpr (OUT_NHWC) {
+    // the block's 128 pixels x n_all channels behind one descriptor (at most 256 KiB); offsets of stored lanes lie inside it
+    T* ob = out + ((size_t)b * hw + p0) * n_all;
+    const int rows = min(kPix, hw - p0);
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, (unsigned)((size_t)rows * n_all * sizeof(T)), 0x00020000);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int oc = 32 * m + 8 * q + 4 * hh;
+        if (live && oc < n_g) {
+          const int el = px * n_all + g * n_g + oc;
+          if constexpr (std::is_same_v<T, float>) {
+            const u32x4 w4 = {__float_as_uint(acc[m][4 * q]), __float_as_uint(acc[m][4 * q + 1]), __float_as_uint(acc[m][4 * q + 2]),
+                              __float_as_uint(acc[m][4 * q + 3])};
+            store_b128_guarded<0>(w4, ro, el * 4, 0);
+          } else {
+            u32x2 w2;
+            w2[0] = Pair<T>::narrow(f32x2{acc[m][4 * q], acc[m][4 * q + 1]});
+            w2[1] = Pair<T>::narrow(f32x2{acc[m][4 * q + 2], acc[m][4 * q + 3]});
+            *reinterpret_cast<u32x2*>(ob + el) = w2;
+          }
+        }
+      }
+  } else {
+    T* ob = out + ((size_t)b * n_all + (size_t)g * n_g) * hw + p0 + px;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int oc = 32 * m + 8 * (e >> 2) + 4 * hh + (e & 3);
+        if (live && oc < n_g) ob[(size_t)oc * hw] = (T)acc[m][e];
+      }
   }
 }
 
@@ -205,28 +293,10 @@ __global__ __launch_bounds__(kBlock) void deform_conv_kernel(const T* __restrict
     float v[8];
     blend<T>(op.cr, v);
     u32x4 xf[P];
-#pragma unroll
-    for (int jp = 0; jp < 4; ++jp) {
-      if constexpr (P == 2) {
-        unsigned hi, mid;
-        split2_hm(v[2 * jp], v[2 * jp + 1], hi, mid);
-        xf[0][jp] = hi;
-        xf[P - 1][jp] = mid;
-      } else {
-        xf[0][jp] = Pair<T>::narrow(f32x2{v[2 * jp], v[2 * jp + 1]});
-      }
-    }
+    operand_of<T>(v, xf);
 #pragma unroll
     for (int m = 0; m < MT; ++m)
-      if (m < s.mt) {
-        if constexpr (P == 2) {
-          acc[m] = mfma16<T>(op.wf[m][P - 1], xf[0], acc[m]);   // smallest terms first
-          acc[m] = mfma16<T>(op.wf[m][0], xf[P - 1], acc[m]);
-          acc[m] = mfma16<T>(op.wf[m][0], xf[0], acc[m]);
-        } else {
-          acc[m] = mfma16<T>(op.wf[m][0], xf[0], acc[m]);
-        }
-      }
+      if (m < s.mt) acc[m] = mfma_parts<T>(op.wf[m], xf, acc[m]);
   };
   Operands opa, opb;
   fetch(0, opa);
@@ -239,41 +309,7 @@ __global__ __launch_bounds__(kBlock) void deform_conv_kernel(const T* __restrict
     }
   }
 
-  // register e of tile m: output channel 32 m + 8 (e >> 2) + 4 hh + (e & 3) of the group, pixel p
-  if constexpr (OUT_NHWC) {
-    // the block's 128 pixels x o channels behind one descriptor (at most 256 KiB); offsets of stored lanes lie inside it
-    T* ob = out + ((size_t)b * hw + p0) * s.o;
-    const int rows = min(kPix, hw - p0);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, (unsigned)((size_t)rows * s.o * sizeof(T)), 0x00020000);
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int oc = 32 * m + 8 * q + 4 * hh;
-        if (live && oc < s.og) {
-          const int el = px * s.o + g * s.og + oc;
-          if constexpr (std::is_same_v<T, float>) {
-            const u32x4 w4 = {__float_as_uint(acc[m][4 * q]), __float_as_uint(acc[m][4 * q + 1]), __float_as_uint(acc[m][4 * q + 2]),
-                              __float_as_uint(acc[m][4 * q + 3])};
-            store_b128_guarded<0>(w4, ro, el * 4, 0);
-          } else {
-            u32x2 w2;
-            w2[0] = Pair<T>::narrow(f32x2{acc[m][4 * q], acc[m][4 * q + 1]});
-            w2[1] = Pair<T>::narrow(f32x2{acc[m][4 * q + 2], acc[m][4 * q + 3]});
-            *reinterpret_cast<u32x2*>(ob + el) = w2;
-          }
-        }
-      }
-  } else {
-    T* ob = out + ((size_t)b * s.o + (size_t)g * s.og) * hw + p;
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int oc = 32 * m + 8 * (e >> 2) + 4 * hh + (e & 3);
-        if (live && oc < s.og) ob[(size_t)oc * hw] = (T)acc[m][e];
-      }
-  }
+  store_tiles<T, OUT_NHWC, MT>(acc, out, b, hw, p0, px, live, hh, g, s.og, s.o);
 }
 
 bool dtype_ok(int d) { return d == DHD_F32 || d == DHD_F16 || d == DHD_BF16; }
@@ -343,6 +379,8 @@ int launch(const void* x, int layout, const float* offset, const float* weight, 
 }
 
 }  // namespace
+
+#include "deform_conv_train.h"
 
 extern "C" {
 

@@ -11,6 +11,8 @@ published definitions (parity UNPINNED: no reference test or fixture covers them
   * mmcv-full 1.5.3 `DCN` (= DeformConv2dPack: zero-initialised 3x3 offset conv + deformable
     convolution v1, offsets ordered (dy, dx) per tap, bilinear sampling with zero padding).
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -102,6 +104,11 @@ class DCN(nn.Module):
     # its float32 result (bf16x3) is within the layer's bar but not bit-identical to the rocBLAS product, and the height logits
     # behind it feed an argmax.
     fused_infer = False
+    # Opt-in (dhd_amd.fused_dcn_training, or DHD_DCN_TRAIN=1 in the environment so that a whole training step can be switched
+    # from outside): forward runs deform_conv.deform_conv -- the fused forward and its HIP backward without column gradients -- in
+    # train and eval mode, with or without grad, where the operator has the shape and the measurement routed that dtype and
+    # layout to it (deform_conv.ROUTED_TRAIN).  Off, or anywhere else: today's path, bit for bit.
+    fused_train = bool(os.environ.get('DHD_DCN_TRAIN'))
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1,
                  deform_groups=1, im2col_step=128, bias=False):
@@ -128,6 +135,16 @@ class DCN(nn.Module):
         probe = torch.empty((0,) + tuple(x.shape[1:]), dtype=self._compute_dtype(), device=x.device)
         return deform_conv_infer_supported(probe, self.weight, self.groups)
 
+    def _train_applies(self, x):
+        """True when forward runs deform_conv (forward and HIP backward) on `x`."""
+        if not (self.fused_train and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.numel() > 0):
+            return False
+        from .deform_conv import deform_conv_train_routed
+        probe = torch.empty((0,) + tuple(x.shape[1:]), dtype=self._compute_dtype(), device=x.device)
+        if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+            probe = probe.contiguous(memory_format=torch.channels_last)
+        return deform_conv_train_routed(probe, self.weight, self.groups)
+
     @staticmethod
     def _compute_dtype():
         cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else torch.float32
@@ -138,6 +155,10 @@ class DCN(nn.Module):
             from .deform_conv import deform_conv_infer
             out = deform_conv_infer(x.to(self._compute_dtype()), self.conv_offset(x), self.weight, self.padding, self.dilation, self.groups)
             return out.contiguous()     # dense NCHW in the compute dtype, what the matmul below hands on
+        if self.fused_train and self._train_applies(x):
+            from .deform_conv import deform_conv
+            out = deform_conv(x.to(self._compute_dtype()), self.conv_offset(x), self.weight, self.padding, self.dilation, self.groups)
+            return out.contiguous()
         b, c, h, w = x.shape
         k = self.k
         g = self.groups
