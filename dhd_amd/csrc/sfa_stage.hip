@@ -22,19 +22,22 @@
 //   * BatchNorm gradient sums are per-plane streaming reductions with double-precision finalisation; the blends are fused with
 //     the BatchNorm affine and the sigmoid.
 // Forward reads x three times and y1/y2 twice; nothing is transposed, there is no NHWC detour.
-// Backward, bf16x3 at C = 128 / 256 on float32 storage without cross-rank statistics (the FOLDED flow, DHD_SFA_BWD_FOLD = 3, the
-// default; T = one (B,C,H,W) tensor).  Both GEMMs of a layer apply the same BatchNorm-backward prologue gy = c0 g + c1 y + c2, so
-// the data gradient runs FIRST and stores gy over g, and the weight gradient reads that one tensor; the load stream this frees
-// carries the tensor a reduction pass of its own used to re-read:
+// Backward, bf16x3 at C = 128 / 256 on float32 storage without cross-rank statistics (DHD_SFA_BWD_FOLD = 7, the default; T = one
+// (B,C,H,W) tensor).  Both GEMMs of a layer apply the same BatchNorm-backward prologue gy = c0 g + c1 y + c2.  Layer 2 runs them in
+// ONE launch on pairs of CUs (sfa_gemm_pair.h): gy2 is staged once per CU and never stored, g1 is summed where it is made.  Layer 1
+// is FOLDED: the data gradient runs first and stores gy over g, the weight gradient reads that one tensor, and the load stream
+// this frees carries the tensor a reduction pass of its own used to re-read:
 //   launch                          reads                          writes
 //   blend2_bn_bwd                   x (2T), y2, gout               g2; BatchNorm-2 sums, go-part of dL/da
-//   pw_gemm_cu EPI 1, WB (dgrad 2)  g2, y2, pass bits              g1, gy2 over g2
-//   pw_wgrad3 FOLD 1 (dW2)          gy2, y1, g1                    partials; sum g1, sum g1 (y1 - mu1) per worker
+//   pw_pair (dgrad 2 + dW2)         g2, y2, y1                     g1; partials; sum g1, sum g1 (y1 - mu1) per pair-worker
 //   wgrad_reduce, bn_backward_rows  partials, worker rows          dW2; BatchNorm-1 backward table, dgamma1, dbeta1
 //   pw_gemm_cu EPI 2, WB (dgrad 1)  g1, y1                         du, gy1 over g1
 //   pw_wgrad3 FOLD 2 (dW1)          gy1, x (2T), du                partials; sum du (x_bev - x_voxel) per (worker, sample)
 //   wgrad_reduce, fc_backward       partials, worker rows          dW1; dL/d(fc)
 //   stage_gx                        y2, gout, du                   gx (2T)
+// 16T of reads and 6T of writes.  DHD_SFA_BWD_FOLD = 3 folds layer 2 as well, in two launches:
+//   pw_gemm_cu EPI 1, WB (dgrad 2)  g2, y2, pass bits              g1, gy2 over g2
+//   pw_wgrad3 FOLD 1 (dW2)          gy2, y1, g1                    partials; sum g1, sum g1 (y1 - mu1) per worker
 // 18T of reads and 7T of writes.  The unfolded flow (every other plan, the phase entry points, DHD_SFA_BWD_FOLD = 0) runs each
 // weight gradient before its data gradient on the pair (g, y) and makes the sums in pair_sums (g1, y1) and blend1_da (x, du):
 // 23T of reads, 5T of writes.
@@ -46,6 +49,7 @@
 #include <type_traits>
 
 #include "sfa_gemm_cu.h"   // pw_gemm_cu: bf16x3 at C = 128 / 256; brings sfa_math.h (the stage's scalar expressions) and vec16.h
+#include "sfa_gemm_pair.h" // pw_pair: data + weight gradient of conv2 on pairs of CUs
 #include "sfa_half.h"      // pw_gemm_cuh / pw_wgrad_h / sfa_onepass_h: the GEMMs of half storage
 #include "sfa_mfma.h"
 
@@ -65,10 +69,13 @@ constexpr int kWgWorkers = 256;   // total pw_wgrad blocks (one per CU)
 // steps [wg_first_step(n, w, W), wg_first_step(n, w + 1, W)), so step s belongs to worker wg_owner(n, s, W).
 __host__ __device__ inline long long wg_first_step(long long n, long long w, long long W) { return n * w / W; }
 __host__ __device__ inline int wg_owner(long long n, long long s, long long W) { return (int)(((s + 1) * W + n - 1) / n) - 1; }
+struct WgFirstStep {   // the same partition for pw_pair_kernel (sfa_gemm_pair.h), whose workers are pairs of workgroups
+  __host__ __device__ long long operator()(long long n, long long w, long long W) const { return wg_first_step(n, w, W); }
+};
 // operand blocks and workers per block of a weight-gradient launch (launch_wgrad) at c channels
 inline int wgrad_blocks(int c) { const int ot = c == 128 ? 128 : 256; return (c / ot) * (c / ot); }
 inline int wgrad_workers(int c) { const int nob = wgrad_blocks(c); return kWgWorkers / nob > 0 ? kWgWorkers / nob : 1; }
-constexpr int kBwdFoldDefault = 3;  // DHD_SFA_BWD_FOLD when the environment does not say (bwd_fold_mode)
+constexpr int kBwdFoldDefault = 7;  // DHD_SFA_BWD_FOLD when the environment does not say (bwd_fold_mode)
 
 __device__ __forceinline__ float block_sum(float v, float* sm) {
   v = group_sum(v, DHD_WAVE);
@@ -1925,14 +1932,29 @@ int stage_forward(const Plan& p, const TS* x, const dhd_sfa_weights* w, TO* out,
   return DHD_OK;
 }
 
-// DHD_SFA_BWD_FOLD = 0 | 1 | 2 | 3: the folded backward flow for no layer / layer 2 / layer 1 / both (A/B switch, read once per
-// process).  Default: see LAB_NOTEBOOK R18.
+// DHD_SFA_BWD_FOLD = 0 | 1 | 2 | 3: the folded backward flow for no layer / layer 2 / layer 1 / both; + 4: layer 2 as ONE launch
+// on pairs of CUs (pw_pair_kernel) in place of its two GEMMs, whatever bit 1 says (A/B switch, read once per process).  Default:
+// see LAB_NOTEBOOK R18, R22.
 int bwd_fold_mode() {
   static const int mode = [] {
     const char* e = getenv("DHD_SFA_BWD_FOLD");
-    return e != nullptr && e[0] >= '0' && e[0] <= '3' && e[1] == 0 ? e[0] - '0' : kBwdFoldDefault;
+    return e != nullptr && e[0] >= '0' && e[0] <= '7' && e[1] == 0 ? e[0] - '0' : kBwdFoldDefault;
   }();
   return mode;
+}
+
+// Layer 2 of the backward in one launch (sfa_gemm_pair.h): g1, this call's conv2 weight gradient and the BatchNorm-1 sums per worker
+int launch_pair(const PairArgs& a, float* gw, int c, hipStream_t st) {
+  const size_t shmem = pair_lds_bytes(c);
+  int rc;
+  if (c == 256) rc = launch_lds<pw_pair_kernel<256, 2, WgFirstStep>>(dim3(kPairGrid), dim3(512), shmem, shmem, st, a);
+  else if (c == 128) rc = launch_lds<pw_pair_kernel<128, 2, WgFirstStep>>(dim3(kPairGrid), dim3(256), shmem, shmem, st, a);
+  else return DHD_EUNSUPPORTED;
+  if (rc != DHD_OK) return rc;
+  const int n = c * c;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(dhd_cdiv(n, DHD_WAVE)), dim3(kEwBlock), 0, st, a.partial, gw, n, kPairWorkers);
+  DHD_LAUNCH_CHECK();
+  return DHD_OK;
 }
 
 // Backward in up to three phases, cut where the two BatchNorm backward passes need their sums (sum g, sum g (y - mu)); `sync`
@@ -1975,7 +1997,8 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
   if (sync && !p.fused_stats) return DHD_EUNSUPPORTED;
   // The folded flow (header comment): per layer, the data gradient first, leaving its prologue's result over g, then the weight
   // gradient on that one tensor, which also makes the sums pair_sums / blend1_da made in passes of their own.  The worker rows
-  // live where scratch is dead: du's region during phase 1, g2's during phase 2.
+  // live where scratch is dead: du's region during phase 1, g2's during phase 2.  Bit 4 of the switch: layer 2 as one launch on
+  // pairs of CUs (launch_pair), under the same gate, its 128 worker rows in du's region too.
   // The gate is `sync == nullptr`, not the entry point: the phase entry points keep the unfolded flow only because they always pass
   // a `sync`; a caller that cut the folded flow into phases would find gy, not g, in g2 / g1 between them.
   int fold = 0;
@@ -2002,7 +2025,18 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
     if (sync) coef_in(tail2, S.loc2, w->conv2_b);
     DHD_LAUNCH_CHECK();
   }
-  if (lo <= 1 && (fold & 1)) {
+  if (lo <= 1 && (fold & 4)) {
+    if constexpr (std::is_same_v<TS, float>) {
+      // g1 = (W2^T dy2) * [z1 > 0], dW2 = dy2 . z1^T and the BatchNorm-1 sums of g1 per worker; g2 stays as it is
+      rc = launch_pair(PairArgs{g2, y2, TF(T.tab_g2), reinterpret_cast<const u32x4*>(sv + S.wp2t), y1, SF(S.scsh1), SF(S.mean1), g1, TF(T.wpart),
+                                rows1, hw, b},
+                       grads->conv2_w, c, st);
+      if (rc != DHD_OK) return rc;
+      const BnRowsJob j1 = {tail1.gamma, tail1.mean, tail1.rstd, tail1.tab, tail1.dgamma, tail1.dbeta, tail1.dbias, w->training, b, hw};
+      hipLaunchKernelGGL(bn_backward_rows_kernel, dim3(c / 4), dim3(kEwBlock), 0, st, rows1, kPairWorkers, j1, c);
+      DHD_LAUNCH_CHECK();
+    }
+  } else if (lo <= 1 && (fold & 1)) {
     if constexpr (std::is_same_v<TS, float>) {
       // g1 = (W2^T dy2) * [z1 > 0]; dy2 stays in g2
       rc = launch_gemm(p, GemmCall<TS>{kDgrad2, g2, y2, cs, c, TF(T.tab_g2), sv + S.wp2t, nullptr, mask, nullptr, g1, y1, SF(S.scsh1), CuBlend{}, 0, g2},
