@@ -16,7 +16,7 @@ from .ema import ModelEMA, MEGVIIEMAHook, SyncbnControlHook, SequentialControlHo
 from .config import Config  # noqa: F401
 from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noqa: F401
 from .amp_weights import HalfWeightCache  # noqa: F401
-from .occ_head import occ_head_infer, occ_head_train  # noqa: F401
+from .occ_head import occ_head_infer, occ_head_train, occ_head_losses  # noqa: F401
 from . import deform_conv  # noqa: F401  (the module, callable as its function deform_conv)
 from .deform_conv import deform_conv_infer, deform_conv_infer_supported, deform_conv_train_supported  # noqa: F401
 from . import window_attn  # noqa: F401  (the module, callable as its function window_attn)
@@ -129,6 +129,21 @@ def fused_occ_head_training(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, predictor)]
     for m in switched:
         m.fused_train = bool(on)
+    return switched
+
+
+def fused_occ_head_loss(model, on=True):
+    """Sets `fused_loss` on every occupancy head (`predictor`) of `model` and returns the heads it switched.  With it
+    `DHD.forward_occ_train` takes `predictor.forward_loss`: final_conv, then the predicter and the three losses as one operator,
+    `occ_head_losses` -- the loss sums ride in the head's forward kernel and the gradient of the logits is computed inside the
+    head's backward kernel -- wherever the operator has the shape and the measurement routed that dtype and layout to it
+    (occ_head.ROUTED_LOSS); every other call keeps today's two calls bit for bit.  It is a switch of its own: it sets none of
+    the other switches, and `predictor.forward` and `predictor.loss` are untouched.  Within the bars of occ_head_train and
+    occ_losses, not bit-identical to them."""
+    from .detector import predictor
+    switched = [m for m in model.modules() if isinstance(m, predictor)]
+    for m in switched:
+        m.fused_loss = bool(on)
     return switched
 
 

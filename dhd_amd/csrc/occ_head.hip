@@ -22,6 +22,7 @@
 //   2 * 9 * P       GEMM-2, k-step s, output tile n, part p: W2[col(r, n)][unit(t, s, h, j)]
 // with P = 2 bf16 parts (high, residual) of a float32 weight, or P = 1 weight rounded to the half type of x.
 #include "sfa_mfma.h"
+#include "occ_loss_math.h"
 
 namespace {
 
@@ -175,11 +176,20 @@ __device__ __forceinline__ void load_x(__amdgpu_buffer_rsrc_t rx, int p, int h, 
   }
 }
 
-template <class T, bool NHWC>
+// the loss epilogue of occ_head_kernel<T, NHWC, true> (occ_head_loss.h)
+__device__ __forceinline__ void loss_terms(const f32x16 (&acc)[kNT], u32x2 lab, u32x2 msk, const float* __restrict__ cw, int ignore,
+                                           float (&sum)[kLossSums]);
+__device__ __forceinline__ void loss_row(float (&sum)[kLossSums], float (*red)[kLossSums], float* __restrict__ row);
+
+// LOSS (occ_head_loss.h): beside the logits, the workgroup's row of the 56 loss sums of its valid voxels -> loss_partial; labels
+// and mask are then required, class_weight and ignore are the loss's.  Without it the three trailing arguments are not read.
+template <class T, bool NHWC, bool LOSS = false>
 __global__ __launch_bounds__(kBlock) void occ_head_kernel(const T* __restrict__ x, const u32x4* __restrict__ stream,
                                                           const float* __restrict__ b2, int dy, int dx, uint8_t* __restrict__ pred,
                                                           float* __restrict__ logits, const uint8_t* __restrict__ labels,
-                                                          const uint8_t* __restrict__ mask, unsigned long long* __restrict__ hist) {
+                                                          const uint8_t* __restrict__ mask, unsigned long long* __restrict__ hist,
+                                                          const float* __restrict__ class_weight, int ignore,
+                                                          float* __restrict__ loss_partial) {
   constexpr int P = kParts<T>, N = kFrags<T>, R = kRing<T>;
   static_assert(N % R == 0, "the ring position of a fragment must not depend on the hidden tile");
   __shared__ unsigned cnt[kClasses * kClasses];
@@ -189,6 +199,11 @@ __global__ __launch_bounds__(kBlock) void occ_head_kernel(const T* __restrict__ 
   if (hist) {
     for (int i = tid; i < kClasses * kClasses; i += kBlock) cnt[i] = 0;
     __syncthreads();
+  }
+  [[maybe_unused]] float lsum[LOSS ? kLossSums : 1];
+  if constexpr (LOSS) {
+#pragma unroll
+    for (int i = 0; i < kLossSums; ++i) lsum[i] = 0.f;   // a wave or a lane past the sample adds nothing
   }
   if (p0 < hw) {
     const int p = p0 + r;
@@ -320,7 +335,13 @@ __global__ __launch_bounds__(kBlock) void occ_head_kernel(const T* __restrict__ 
           if (tl < kClasses && m != 0) atomicAdd(&cnt[tl * kClasses + arg[z]], 1u);
         }
       }
+      if constexpr (LOSS)
+        loss_terms(acc, *reinterpret_cast<const u32x2*>(labels + vox), *reinterpret_cast<const u32x2*>(mask + vox), class_weight, ignore, lsum);
     }
+  }
+  if constexpr (LOSS) {
+    __shared__ float lred[kBlock / 64][kLossSums];
+    loss_row(lsum, lred, loss_partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kLossSums);
   }
   if (hist) {
     __syncthreads();
@@ -349,7 +370,7 @@ int launch(const void* x, const dhd_occ_head_weights* w, int b, int dy, int dx, 
   DHD_LAUNCH_CHECK();
   hipLaunchKernelGGL((occ_head_kernel<T, NHWC>), dim3(dhd_cdiv((long)dy * dx, kCellsPerBlock), b), dim3(kBlock), 0, st,
                      static_cast<const T*>(x), stream, w->b2, dy, dx, pred, logits, labels, mask,
-                     reinterpret_cast<unsigned long long*>(hist));
+                     reinterpret_cast<unsigned long long*>(hist), (const float*)nullptr, 0, (float*)nullptr);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -394,3 +415,5 @@ int dhd_occ_head_infer(const void* x, int x_dtype, int layout, const dhd_occ_hea
 
 // the training half: the recompute backward and its dhdo_* entry points (the forward in training is dhd_occ_head_infer itself)
 #include "occ_head_train.h"
+// the head and its three losses as one operator: the forward's loss epilogue, the backward with the loss gradient, dhdl_*
+#include "occ_head_loss.h"

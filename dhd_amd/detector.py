@@ -550,6 +550,46 @@ class predictor(nn.Module):
             loss_voxel_sem_scal=self.weight_sem * sem_scal_loss_with_mask(preds, sem, mask),
             loss_voxel_geo_scal=self.weight_geo * geo_scal_loss_with_mask(preds, sem, mask, non_empty_idx=17))
 
+    # Opt-in (dhd_amd.fused_occ_head_loss, or DHD_OCC_HEAD_LOSS=1 in the environment so that a whole training step can be switched
+    # from outside): DHD.forward_occ_train calls forward_loss instead of forward and loss, and forward_loss sends final_conv's
+    # output to occ_head.occ_head_losses -- head and losses as one operator -- where the operator has the shape and the
+    # measurement routed that dtype and layout to it (occ_head.ROUTED_LOSS).  Off, or anywhere else: today's two calls, bit for bit.
+    fused_loss = bool(os.environ.get('DHD_OCC_HEAD_LOSS'))
+
+    def _loss_applies(self, x):
+        """True when forward_loss runs occ_head_losses on final_conv's output `x`."""
+        if not (self.fused_loss and self.use_predicter and self.use_mask and self.class_balance and torch.is_tensor(x) and x.is_cuda):
+            return False
+        from . import occ_head
+        return occ_head.loss_routed(x, self.predicter[0].weight, self.predicter[2].weight, self.Dz)
+
+    def forward_loss(self, img_feats, voxel_semantics, mask_camera):
+        """loss(forward(img_feats), voxel_semantics, mask_camera): the same dict with the same weights applied.  Where
+        _loss_applies, the predicter and the three losses run as occ_head.occ_head_losses; anywhere else forward's own steps
+        after final_conv and loss run as they do today."""
+        x = self.final_conv(img_feats)
+        if self._loss_applies(x):
+            from . import occ_head
+            lin1, lin2 = self.predicter[0], self.predicter[2]
+            cw = getattr(self, '_cls_weights_dev', None)   # loss's device copy, made once
+            if cw is None or cw.device != x.device:
+                cw = self._cls_weights_dev = self.cls_weights.to(device=x.device, dtype=torch.float32)
+            l_ce, l_sem, l_geo = occ_head.occ_head_losses(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, voxel_semantics, mask_camera, cw,
+                                                          dz=self.Dz, ignore_index=self.loss_occ.ignore_index, non_empty_idx=17)
+            scale = getattr(self.loss_occ, 'loss_weight', 1.0)
+            return dict(loss_occ=self.weight_ce * scale * l_ce, loss_voxel_sem_scal=self.weight_sem * l_sem,
+                        loss_voxel_geo_scal=self.weight_geo * l_geo)
+        if self._train_applies(x):                         # forward's steps after final_conv, as they stand there
+            from . import occ_head
+            lin1, lin2 = self.predicter[0], self.predicter[2]
+            logits = occ_head.occ_head_train(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, self.Dz)
+        else:
+            logits = x.permute(0, 3, 2, 1)
+            if self.use_predicter:
+                b, dx, dy = logits.shape[:3]
+                logits = self.predicter(logits).view(b, dx, dy, self.Dz, self.num_classes)
+        return self.loss(logits, voxel_semantics, mask_camera)
+
     # Opt-in: in eval mode with nothing to differentiate DHD.simple_test_occ takes predict_occ's fused operator instead of
     # forward + get_occ.  Off by default: at near-ties of the two largest logits its class can differ from rocBLAS float32's.
     fused_infer = False
@@ -778,6 +818,8 @@ class DHD(nn.Module):
         return x_2d, x_3d, None, depth, height
 
     def forward_occ_train(self, img_feats, voxel_semantics, mask_camera):
+        if getattr(self.occ_head, 'fused_loss', False):    # predictor's switch: head and losses as one operator where it is routed
+            return self.occ_head.forward_loss(self.mixed_feats(img_feats), voxel_semantics, mask_camera)
         return self.occ_head.loss(self.occ_logits(img_feats), voxel_semantics, mask_camera)
 
     def forward_train(self, points=None, img_metas=None, img_inputs=None, **kwargs):

@@ -5,12 +5,14 @@ The (cells, 512) hidden and the (cells, 288) logits of the module formulation ne
 
 In training the same MLP is `occ_head_train` (csrc/occ_head_train.h, capi/dhd_amd_occ_train.h): an autograd function whose
 forward is the inference operator writing float32 logits, saving x and the parameters and nothing of hidden size, and whose
-backward recomputes the hidden tile by tile in one HIP call -- `predictor.fused_train`'s route."""
+backward recomputes the hidden tile by tile in one HIP call -- `predictor.fused_train`'s route.  `occ_head_losses`
+(csrc/occ_head_loss.h, capi_occ_loss/dhd_amd_occ_head_loss.h) is that function with the head's three losses inside: the loss sums
+ride in the forward kernel and the loss gradient in the backward kernel -- `predictor.fused_loss`'s route."""
 import ctypes as C
 
 import torch
 
-from . import _lib, _occ_train
+from . import _lib, _occ_loss_head, _occ_train
 from .occ_loss import NUM_CLASSES
 from .trace import traced
 
@@ -276,3 +278,174 @@ def occ_head_train(x, w1, b1, w2, b2, dz=16):
         if not (torch.is_tensor(p) and p.is_cuda and tuple(p.shape) == shape):
             raise _lib.DhdError(f'occ_head_train: {name} must be a GPU tensor of shape {shape}')
     return _OccHeadTrain.apply(x, w1, b1, w2, b2, dz)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Training: the head and its three losses as one operator (csrc/occ_head_loss.h, capi_occ_loss/dhd_amd_occ_head_loss.h)
+
+# Which (x dtype, layout) entries `predictor.fused_loss` routes to `occ_head_losses` (layout 0 = NCHW, 1 = channels_last): by
+# ROUTED_TRAIN's rule, True only where forward + backward of head and losses, the weight packs and the torch weight-gradient
+# GEMMs included, beat occ_head_train + occ_loss.occ_losses by more than the larger min-max spread of the two paths at
+# (4, 256, 200, 200) with a 70 % camera mask (experiments/occ_head_loss_bench.py -> profiles/r23/occ_head_loss.json).
+# Medians in us per forward + backward, fused against the parent path (larger min-max spread of the two):
+#   float32        NCHW 3352 against 3310 (13),   channels_last 4010 against 3926 (19)
+#   fp16 autocast  NCHW 1465 against 1462 (52),   channels_last 1668 against 1700 (28)
+#   bf16 autocast  NCHW 1465 against 1466 (42),   channels_last 1675 against 1704 (35)
+# The forward alone: 410 / 429 / 285 / 284 / 281 / 282 against 405 / 432 / 276 / 278 / 274 / 279.  The two loss passes the operator
+# removes cost the parent path about 110 us of a step, and the softmax epilogue and prologue cost the fused kernels as much: one
+# entry wins by more than the spread (fp16 channels_last, by 32 us), bf16 channels_last wins by less (29 against 35), the NCHW
+# half entries tie and float32 loses (it writes and re-reads the same float32 g, with the softmax on top).  Held between forward
+# and backward: 176 MiB either way; peak of a step 659 MiB either way under autocast, 1138 against 962 MiB in float32 (g is
+# allocated beside act and dhid instead of before them).
+ROUTED_LOSS = {
+    (torch.float32, 0): False, (torch.float32, 1): False,
+    (torch.float16, 0): False, (torch.float16, 1): True,
+    (torch.bfloat16, 0): False, (torch.bfloat16, 1): False,
+}
+
+
+def loss_supported(x, w1, w2, dz=16):
+    """True when `occ_head_losses` itself takes this call: occ_head_train's set (train_supported)."""
+    if not train_supported(x, w1, w2, dz):
+        return False
+    return bool(_occ_loss_head.value('dhdl_occ_head_loss_supported', x.shape[1], w1.shape[0], dz, w2.shape[0] // dz,
+                                     _lib.DTYPE_CODE[x.dtype], _train_layout(x)))
+
+
+def loss_routed(x, w1, w2, dz=16):
+    """True when a `predictor` with `fused_loss` on sends final_conv's output `x` to `occ_head_losses`."""
+    if not loss_supported(x, w1, w2, dz):
+        return False
+    return ROUTED_LOSS.get((x.dtype, _train_layout(x)), False)
+
+
+def _voxel_bytes(t, n, name):
+    """labels / mask as the kernels read them: uint8, one per voxel, dense and aligned."""
+    t = _lib.dense16(t.reshape(-1).to(torch.uint8))
+    if t.numel() != n:
+        raise _lib.DhdError(f'occ_head_losses: {name} must have one element per voxel ({n}), got {t.numel()}')
+    return t
+
+
+def occ_head_loss_forward(x, w1, b1, w2, b2, labels, mask, cw, dz=16, ignore_index=255, non_empty_idx=17):
+    """One dhdl_occ_head_loss_forward call on dense, aligned GPU tensors: x (B, 256, Dy, Dx) NCHW or channels_last, the
+    parameters, labels and mask uint8 (B * Dx * Dy * dz,), cw float32 (18,) -> (logits (B, Dx, Dy, dz, 18) float32, losses (3,)
+    float32, workspace).  Allocates its outputs and its scratch; nothing is cached."""
+    b, c, dy, dx = x.shape
+    layout = _layout_of(x)
+    if layout is None:
+        raise _lib.DhdError('occ_head_loss_forward: x must be dense, NCHW or channels_last')
+    code, dev = _lib.dtype_code(x.dtype), x.device
+    with torch.cuda.device(dev):
+        wts, held = _weights(w1, b1, w2, b2, c, dz)
+        fwd, bwd = C.c_size_t(), C.c_size_t()
+        _occ_loss_head.call('dhdl_occ_head_loss_scratch_bytes', C.byref(wts), code, b, dy, dx, C.byref(fwd), C.byref(bwd))
+        scratch = torch.empty(fwd.value, dtype=torch.uint8, device=dev)
+        logits = torch.empty(b, dx, dy, dz, wts.n_classes, dtype=torch.float32, device=dev)
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        ws = torch.empty(_occ_loss_head.value('dhdl_occ_head_loss_workspace_bytes'), dtype=torch.uint8, device=dev)
+        _occ_loss_head.call('dhdl_occ_head_loss_forward', _lib.ptr(x), code, layout, C.byref(wts), b, dy, dx, _lib.ptr(labels),
+                            _lib.ptr(mask), _lib.ptr(cw), ignore_index, non_empty_idx, _lib.ptr(logits), _lib.ptr(losses), _lib.ptr(ws),
+                            _lib.ptr(scratch), fwd.value, _lib.stream_ptr(dev))
+    return logits, losses, ws
+
+
+def occ_head_loss_backward(x, logits, labels, mask, cw, ws, glosses, w1, b1, w2, dz=16, ignore_index=255, non_empty_idx=17,
+                           operands=True):
+    """One dhdl_occ_head_loss_backward call: the forward's inputs, logits and workspace and glosses (3,) float32 on the device
+    -> (dx, db1, db2, act, dhid, g) as occ_head_backward returns them, g in ghalf's place: for a float32 x always the float32
+    dL/dlogits (the kernel's own operand), for a half x dL/dlogits rounded once, with `operands` only."""
+    b, c, dy, dx = x.shape
+    layout = _layout_of(x)
+    if layout is None:
+        raise _lib.DhdError('occ_head_loss_backward: x must be dense, NCHW or channels_last')
+    code, dev, cells = _lib.dtype_code(x.dtype), x.device, b * dy * dx
+    hidden, cols = w1.shape[0], w2.shape[0]
+    with torch.cuda.device(dev):
+        wts, held = _weights(w1, b1, w2, None, c, dz)
+        dxo = torch.empty_like(x)
+        db1 = torch.empty(hidden, dtype=torch.float32, device=dev)
+        db2 = torch.empty(cols, dtype=torch.float32, device=dev)
+        act = dhid = g = None
+        if operands:
+            act = torch.empty((cells, hidden), dtype=x.dtype, device=dev)
+            dhid = torch.empty((cells, hidden), dtype=x.dtype, device=dev)
+        if operands or x.dtype == torch.float32:
+            g = torch.empty((cells, cols), dtype=x.dtype, device=dev)
+        fwd, bwd = C.c_size_t(), C.c_size_t()
+        _occ_loss_head.call('dhdl_occ_head_loss_scratch_bytes', C.byref(wts), code, b, dy, dx, C.byref(fwd), C.byref(bwd))
+        scratch = torch.empty(bwd.value, dtype=torch.uint8, device=dev)
+        _occ_loss_head.call('dhdl_occ_head_loss_backward', _lib.ptr(x), code, layout, C.byref(wts), b, dy, dx, _lib.ptr(logits),
+                            _lib.ptr(labels), _lib.ptr(mask), _lib.ptr(cw), ignore_index, non_empty_idx, _lib.ptr(glosses), _lib.ptr(ws),
+                            _lib.ptr(dxo), _lib.ptr(db1), _lib.ptr(db2), _lib.ptr(act), _lib.ptr(dhid), _lib.ptr(g), _lib.ptr(scratch),
+                            bwd.value, _lib.stream_ptr(dev))
+    return dxo, db1, db2, act, dhid, g
+
+
+class _OccHeadLosses(torch.autograd.Function):
+    """The three losses of the predicter MLP's logits; saves the dense x, the parameters, the float32 logits, the uint8 labels and
+    mask, the class weights and the workspace of totals.  The backward is one dhdl_occ_head_loss_backward call and torch's two
+    weight-gradient GEMMs on the operands it writes, as in _OccHeadTrain.backward."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, labels, mask, cw, dz, ignore_index, non_empty_idx):
+        xd, layout = _dense_in_layout(x.detach())
+        logits, losses, ws = occ_head_loss_forward(xd, w1, b1, w2, b2, labels, mask, cw, dz, ignore_index, non_empty_idx)
+        ctx.save_for_backward(xd, w1, b1, w2, b2, logits, labels, mask, cw, ws)
+        ctx.args = (dz, ignore_index, non_empty_idx)
+        return losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @traced('dhd.occ_head.losses')
+    def backward(ctx, glosses):
+        x, w1, b1, w2, b2, logits, labels, mask, cw, ws = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gl = glosses.float().contiguous()
+        with torch.autocast('cuda', enabled=False):
+            dx, db1, db2, act, dhid, g = occ_head_loss_backward(x, logits, labels, mask, cw, ws, gl, w1, b1, w2, *ctx.args,
+                                                                operands=need[1] or need[3])
+            dw1 = dw2 = None
+            if need[1]:
+                b, c, dy, dxs = x.shape
+                if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+                    dw1 = dhid.t() @ x.permute(0, 2, 3, 1).reshape(-1, c)          # a view: x's pixels are dhid's rows
+                else:                                                               # NCHW: one product per sample, summed
+                    per = torch.bmm(dhid.view(b, dy * dxs, -1).transpose(1, 2), x.reshape(b, c, dy * dxs).transpose(1, 2))
+                    dw1 = per[0] if b == 1 else per.sum(0, dtype=torch.float32)
+                dw1 = dw1.to(w1.dtype)
+            if need[3]:
+                dw2 = (g.t() @ act).to(w2.dtype)
+        return (dx if need[0] else None, dw1, db1.to(b1.dtype) if need[2] else None, dw2, db2.to(b2.dtype) if need[4] else None,
+                None, None, None, None, None, None)
+
+
+def occ_head_losses(x, w1, b1, w2, b2, labels, mask_camera, class_weight, dz=16, ignore_index=255, non_empty_idx=17):
+    """(loss_occ, loss_voxel_sem_scal, loss_voxel_geo_scal) before the head's weight_* factors, of the predicter MLP on
+    final_conv's output: occ_loss.occ_losses(occ_head_train(x, ...), labels, mask_camera, class_weight) as one operator,
+    differentiable in x and the four parameters.  x (B, 256, Dy, Dx) float32 / float16 / bfloat16, NCHW or channels_last;
+    labels / mask_camera (B, Dx, Dy, dz) of any integer or bool dtype (converted to uint8 once); class_weight (18,).
+
+    The forward writes the float32 logits (occ_head_train's bytes) and, from the registers that hold them, the 56 sums the losses
+    are functions of; the backward computes dL/dlogits in the head's backward kernel from the saved logits, the labels and the
+    totals, so neither of occ_loss's two passes runs and no float32 gradient of the logits exists for a half x.  Saved between
+    forward and backward: x, the parameters, the logits, the uint8 labels and mask, and 448 bytes of totals.  The upstream
+    gradient is read on the device: a loss scale costs nothing, and forward + backward can be captured into a HIP graph.  Works
+    under torch.autocast and checkpoint(..., use_reentrant=False).  No atomics: a repeated call gives the same bytes.  HIP only:
+    a CPU tensor or an unsupported shape raises DhdError."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.DhdError(f'occ_head_losses: x must live on the GPU: dhd_amd runs only as HIP kernels (got {getattr(x, "device", None)})')
+    if not loss_supported(x, w1, w2, dz):
+        raise _lib.DhdError(f'occ_head_losses: no operator for x {tuple(x.shape)} of {x.dtype} with weights {tuple(w1.shape)}, '
+                            f'{tuple(w2.shape)} and dz {dz}')
+    for p, shape, name in ((w1, (512, 256), 'w1'), (b1, (512,), 'b1'), (w2, (dz * NUM_CLASSES, 512), 'w2'), (b2, (dz * NUM_CLASSES,), 'b2')):
+        if not (torch.is_tensor(p) and p.is_cuda and tuple(p.shape) == shape):
+            raise _lib.DhdError(f'occ_head_losses: {name} must be a GPU tensor of shape {shape}')
+    n = x.shape[0] * x.shape[2] * x.shape[3] * dz
+    labels = _voxel_bytes(labels.to(x.device), n, 'labels')
+    mask = _voxel_bytes(mask_camera.to(x.device), n, 'mask_camera')
+    cw = _lib.dense16(class_weight.detach().to(device=x.device, dtype=torch.float32))
+    if cw.numel() != NUM_CLASSES:
+        raise _lib.DhdError(f'occ_head_losses: class_weight must have {NUM_CLASSES} elements')
+    out = _OccHeadLosses.apply(x, w1, b1, w2, b2, labels, mask, cw, dz, int(ignore_index), int(non_empty_idx))
+    return out[0], out[1], out[2]
