@@ -16,6 +16,7 @@ from .ema import ModelEMA, MEGVIIEMAHook, SyncbnControlHook, SequentialControlHo
 from .config import Config  # noqa: F401
 from .checkpoint import load_checkpoint, load_state_dict, save_checkpoint  # noqa: F401
 from .amp_weights import HalfWeightCache  # noqa: F401
+from .optim import FusedAdamW, DynamicLossScale, build_optimizer  # noqa: F401
 from .occ_head import occ_head_infer, occ_head_train, occ_head_losses  # noqa: F401
 from . import deform_conv  # noqa: F401  (the module, callable as its function deform_conv)
 from .deform_conv import deform_conv_infer, deform_conv_infer_supported, deform_conv_train_supported  # noqa: F401

@@ -83,3 +83,6 @@ extern "C" int dhd_ema_update_dev(const uint64_t* ema_addr, const uint64_t* mode
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
+
+// The optimizer step that carries the EMA in its sweep (dhdw_*): kernels and entry points, behind ema1().
+#include "optim_step.h"

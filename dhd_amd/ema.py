@@ -89,6 +89,53 @@ class ModelEMA:
         self.updates += 1
         self._set_decay_dev(self.decay(self.updates))
 
+    # ---- an update shared with the optimizer (dhd_amd.optim.FusedAdamW(ema=...)): the optimizer's sweep moves the EMA of the
+    # parameters it updates, in the launch that has their new values in registers; the host side of the update and the rest of
+    # the state (buffers, frozen parameters) stay here.  update() does not use any of this.
+
+    def pairs(self, model):
+        """(EMA tensor, model tensor) of every entry of the state, in state-dict order."""
+        ours, theirs = _state_tensors(self.ema), _state_tensors(_inner(model))
+        if len(ours) != len(theirs):
+            raise KeyError('ModelEMA: the model state no longer matches the EMA copy')
+        return list(zip(ours, theirs))
+
+    def begin_update(self, devices=()):
+        """Host side of ONE update some of whose tensors another launch sweeps: the count moves on and {d, 1 - d} is placed on
+        `devices`, where such a launch reads it; returns d.  While a graph is being captured nothing moves -- the count and the
+        decay belong to the replays (advance()) -- and d is the decay the next update will have."""
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            if any(dev not in self._decay_dev for dev in devices):
+                raise _lib.DhdError('ModelEMA: run one eager update (a warm-up step) before capturing it into a graph')
+            self.captured = True
+            return self.decay(self.updates + 1)
+        self.updates += 1
+        d = self.decay(self.updates)
+        for dev in devices:
+            if dev not in self._decay_dev:
+                self._decay_dev[dev] = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._set_decay_dev(d)
+        return d
+
+    def update_rest(self, model, covered, d):
+        """The tensors of the update begun by begin_update() that the other launch left out: every entry of the state whose
+        model tensor is not in `covered` (a set of id()s), by update()'s own expression and launch, over a table of its own."""
+        with torch.no_grad():
+            rest = [(v, m) for v, m in self.pairs(model) if id(m) not in covered]
+            key = [v.data_ptr() for v, _ in rest] + [m.data_ptr() for _, m in rest]
+            if key != getattr(self, '_rest_key', None):
+                self._rest_cpu, self._rest_tables = self._plan([v for v, _ in rest], [m for _, m in rest])
+                self._rest_key = key
+            for v, m in self._rest_cpu:
+                v *= d
+                v += (1.0 - d) * m
+            for dev, tab in self._rest_tables.items():
+                if dev not in self._decay_dev:
+                    raise _lib.DhdError('ModelEMA.update_rest: begin_update() was not given this device')
+                with torch.cuda.device(dev):
+                    _lib.check(_lib.load().dhd_ema_update_dev(_lib.ptr(tab.ema_addr), _lib.ptr(tab.model_addr), _lib.ptr(tab.len), tab.n,
+                                                              _lib.ptr(self._decay_dev[dev]), _lib.stream_ptr(dev)), 'dhd_ema_update_dev')
+
     def _plan(self, ours, theirs):
         """Sort the state into CPU pairs and per-device chunk tables (redone only when a tensor moved)."""
         cpu, by_dev = [], {}
