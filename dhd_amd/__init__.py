@@ -26,6 +26,7 @@ from .swin_glue import layer_norm_rows, window_reverse_add, swin_glue_supported 
 from . import swin_ffn  # noqa: F401  (the module, callable as its function swin_ffn)
 from .swin_ffn import swin_ffn_infer, swin_ffn_supported, swin_ffn_train_supported, swin_ffn_train_wide_supported  # noqa: F401
 from .swin_seam import patch_merge_norm, patch_embed_norm, swin_seam_supported  # noqa: F401
+from .unet_seam import max_pool2x2, conv_transpose2x2_cat, unet_seam_supported, unet_seam_routed  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'
@@ -173,6 +174,21 @@ def fused_swin_seams(model, on=True):
     do not set it and it sets none of theirs.  Within the layer's bar of torch's LayerNorm, not bit-identical."""
     from .swin import PatchEmbed, PatchMerging
     switched = [m for m in model.modules() if isinstance(m, (PatchEmbed, PatchMerging))]
+    for m in switched:
+        m.fused_seam = bool(on)
+    return switched
+
+
+def fused_unet_seams(model, on=True):
+    """Sets `fused_seam` on every `_Down` and `_Up` of the UNets of `model` and returns the modules it switched.  With it the
+    MaxPool2d(2) of `_Down` runs as `max_pool2x2` -- no index tensor, the backward recomputes the winners from the skip tensor --
+    and ConvTranspose2d + pad + cat of `_Up` (bilinear=False) as `conv_transpose2x2_cat`, one launch that writes the concatenated
+    tensor, in train and eval mode, with or without grad, wherever the tensors are on the GPU, the operator has the shape
+    (unet_seam_supported) and the measurement routed that channel count, dtype and layout to it (unet_seam.ROUTED); every other
+    call, and `_Up` with bilinear=True, keeps today's path bit for bit.  It is a switch of its own: it sets none of the other
+    switches.  The pooling is torch's bit for bit; the up seam is within the layer's bar of today's path, not bit-identical."""
+    from .detector import _Down, _Up
+    switched = [m for m in model.modules() if isinstance(m, (_Down, _Up))]
     for m in switched:
         m.fused_seam = bool(on)
     return switched

@@ -224,3 +224,6 @@ int dhd_upsample_bilinear_backward(const void* grad_y, int dtype, int layout, in
 }
 
 }  // extern "C"
+
+// the seams of the UNets' other decoder form (ConvTranspose2d) and of their encoder: the dhdn_* surface
+#include "unet_seam.h"

@@ -338,15 +338,25 @@ class _DoubleConv(nn.Module):
 
 
 class _Down(nn.Module):
+    # A/B switch (dhd_amd.fused_unet_seams): the pooling as unet_seam.max_pool2x2 where the measurement routed it
+    fused_seam = bool(os.environ.get('DHD_UNET_SEAMS'))
+
     def __init__(self, cin, cout):
         super().__init__()
         self.maxpool_conv = nn.Sequential(nn.MaxPool2d(2), _DoubleConv(cin, cout))
 
     def forward(self, x):
+        if self.fused_seam and x.is_cuda:
+            from . import unet_seam
+            if unet_seam.unet_seam_routed(x, 'pool') and unet_seam.unet_seam_supported(x, 'pool'):
+                return self.maxpool_conv[1](unet_seam.max_pool2x2(x))
         return self.maxpool_conv(x)
 
 
 class _Up(nn.Module):
+    # A/B switch (dhd_amd.fused_unet_seams): ConvTranspose2d + pad + cat as unet_seam.conv_transpose2x2_cat where routed
+    fused_seam = bool(os.environ.get('DHD_UNET_SEAMS'))
+
     def __init__(self, cin, cout, bilinear):
         super().__init__()
         if bilinear:
@@ -357,6 +367,10 @@ class _Up(nn.Module):
             self.conv = _DoubleConv(cin, cout)
 
     def forward(self, x1, x2):
+        if self.fused_seam and x1.is_cuda and isinstance(self.up, nn.ConvTranspose2d):
+            from . import unet_seam
+            if unet_seam.unet_seam_routed(x1, 'up') and unet_seam.unet_seam_supported(x1, 'up', x2, self.up.weight):
+                return self.conv(unet_seam.conv_transpose2x2_cat(x1, x2, self.up.weight, self.up.bias))
         x1 = self.up(x1)
         dy, dx = x2.size(2) - x1.size(2), x2.size(3) - x1.size(3)
         x1 = F.pad(x1, [dx // 2, dx - dx // 2, dy // 2, dy - dy // 2])
