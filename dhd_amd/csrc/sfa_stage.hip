@@ -22,20 +22,24 @@
 //   * BatchNorm gradient sums are per-plane streaming reductions with double-precision finalisation; the blends are fused with
 //     the BatchNorm affine and the sigmoid.
 // Forward reads x three times and y1/y2 twice; nothing is transposed, there is no NHWC detour.
-// Backward, bf16x3 at C = 128 / 256 on float32 storage without cross-rank statistics (DHD_SFA_BWD_FOLD = 7, the default; T = one
-// (B,C,H,W) tensor).  Both GEMMs of a layer apply the same BatchNorm-backward prologue gy = c0 g + c1 y + c2.  Layer 2 runs them in
-// ONE launch on pairs of CUs (sfa_gemm_pair.h): gy2 is staged once per CU and never stored, g1 is summed where it is made.  Layer 1
-// is FOLDED: the data gradient runs first and stores gy over g, the weight gradient reads that one tensor, and the load stream
-// this frees carries the tensor a reduction pass of its own used to re-read:
+// Backward, bf16x3 at C = 128 / 256 on float32 storage without cross-rank statistics (DHD_SFA_BWD_FOLD = 15, the default; T = one
+// (B,C,H,W) tensor).  Both GEMMs of a layer apply the same BatchNorm-backward prologue gy = c0 g + c1 y + c2, and each layer runs
+// them in ONE launch on pairs of CUs: gy is staged once per CU and never stored.  Layer 2 (sfa_gemm_pair.h) sums g1 where it is
+// made; layer 1 (sfa_gemm_pair1.h) blends x into the weight gradient's operand, sums du (x_bev - x_voxel) where du is made and
+// leaves g1 alone:
 //   launch                          reads                          writes
 //   blend2_bn_bwd                   x (2T), y2, gout               g2; BatchNorm-2 sums, go-part of dL/da
 //   pw_pair (dgrad 2 + dW2)         g2, y2, y1                     g1; partials; sum g1, sum g1 (y1 - mu1) per pair-worker
 //   wgrad_reduce, bn_backward_rows  partials, worker rows          dW2; BatchNorm-1 backward table, dgamma1, dbeta1
-//   pw_gemm_cu EPI 2, WB (dgrad 1)  g1, y1                         du, gy1 over g1
-//   pw_wgrad3 FOLD 2 (dW1)          gy1, x (2T), du                partials; sum du (x_bev - x_voxel) per (worker, sample)
+//   pw_pair1 (dgrad 1 + dW1)        g1, y1, x (2T)                 du; partials; sum du (x_bev - x_voxel) per (pair-worker, sample)
 //   wgrad_reduce, fc_backward       partials, worker rows          dW1; dL/d(fc)
 //   stage_gx                        y2, gout, du                   gx (2T)
-// 16T of reads and 6T of writes.  DHD_SFA_BWD_FOLD = 3 folds layer 2 as well, in two launches:
+// 14T of reads and 5T of writes (what the pairs' second CU reads again is not counted: it is the same tile at the same time).
+// DHD_SFA_BWD_FOLD = 7 FOLDS layer 1 in two launches instead: the data gradient runs first and stores gy over g, the weight gradient
+// reads that one tensor, and the load stream this frees carries the tensor a reduction pass of its own used to re-read:
+//   pw_gemm_cu EPI 2, WB (dgrad 1)  g1, y1                         du, gy1 over g1
+//   pw_wgrad3 FOLD 2 (dW1)          gy1, x (2T), du                partials; sum du (x_bev - x_voxel) per (worker, sample)
+// 16T of reads and 6T of writes.  DHD_SFA_BWD_FOLD = 3 folds layer 2 as well:
 //   pw_gemm_cu EPI 1, WB (dgrad 2)  g2, y2, pass bits              g1, gy2 over g2
 //   pw_wgrad3 FOLD 1 (dW2)          gy2, y1, g1                    partials; sum g1, sum g1 (y1 - mu1) per worker
 // 18T of reads and 7T of writes.  The unfolded flow (every other plan, the phase entry points, DHD_SFA_BWD_FOLD = 0) runs each
@@ -50,6 +54,7 @@
 
 #include "sfa_gemm_cu.h"   // pw_gemm_cu: bf16x3 at C = 128 / 256; brings sfa_math.h (the stage's scalar expressions) and vec16.h
 #include "sfa_gemm_pair.h" // pw_pair: data + weight gradient of conv2 on pairs of CUs
+#include "sfa_gemm_pair1.h" // pw_pair1: the same for conv1, with the blend prologue and the dL/da sums
 #include "sfa_half.h"      // pw_gemm_cuh / pw_wgrad_h / sfa_onepass_h: the GEMMs of half storage
 #include "sfa_mfma.h"
 
@@ -75,7 +80,7 @@ struct WgFirstStep {   // the same partition for pw_pair_kernel (sfa_gemm_pair.h
 // operand blocks and workers per block of a weight-gradient launch (launch_wgrad) at c channels
 inline int wgrad_blocks(int c) { const int ot = c == 128 ? 128 : 256; return (c / ot) * (c / ot); }
 inline int wgrad_workers(int c) { const int nob = wgrad_blocks(c); return kWgWorkers / nob > 0 ? kWgWorkers / nob : 1; }
-constexpr int kBwdFoldDefault = 7;  // DHD_SFA_BWD_FOLD when the environment does not say (bwd_fold_mode)
+constexpr int kBwdFoldDefault = 15;  // DHD_SFA_BWD_FOLD when the environment does not say (bwd_fold_mode)
 
 __device__ __forceinline__ float block_sum(float v, float* sm) {
   v = group_sum(v, DHD_WAVE);
@@ -1933,12 +1938,16 @@ int stage_forward(const Plan& p, const TS* x, const dhd_sfa_weights* w, TO* out,
 }
 
 // DHD_SFA_BWD_FOLD = 0 | 1 | 2 | 3: the folded backward flow for no layer / layer 2 / layer 1 / both; + 4: layer 2 as ONE launch
-// on pairs of CUs (pw_pair_kernel) in place of its two GEMMs, whatever bit 1 says (A/B switch, read once per process).  Default:
-// see LAB_NOTEBOOK R18, R22.
+// on pairs of CUs (pw_pair_kernel) in place of its two GEMMs, whatever bit 1 says; + 8: the same for layer 1 (pw_pair1_kernel),
+// whatever bit 2 says.  Decimal 0 .. 15, anything else is the default (A/B switch, read once per process).  Default: see
+// LAB_NOTEBOOK R18, R22, R26.
 int bwd_fold_mode() {
   static const int mode = [] {
     const char* e = getenv("DHD_SFA_BWD_FOLD");
-    return e != nullptr && e[0] >= '0' && e[0] <= '7' && e[1] == 0 ? e[0] - '0' : kBwdFoldDefault;
+    if (e == nullptr || e[0] < '0' || e[0] > '9') return kBwdFoldDefault;
+    if (e[1] == 0) return e[0] - '0';
+    if (e[0] == '1' && e[1] >= '0' && e[1] <= '5' && e[2] == 0) return 10 + (e[1] - '0');
+    return kBwdFoldDefault;
   }();
   return mode;
 }
@@ -1949,6 +1958,21 @@ int launch_pair(const PairArgs& a, float* gw, int c, hipStream_t st) {
   int rc;
   if (c == 256) rc = launch_lds<pw_pair_kernel<256, 2, WgFirstStep>>(dim3(kPairGrid), dim3(512), shmem, shmem, st, a);
   else if (c == 128) rc = launch_lds<pw_pair_kernel<128, 2, WgFirstStep>>(dim3(kPairGrid), dim3(256), shmem, shmem, st, a);
+  else return DHD_EUNSUPPORTED;
+  if (rc != DHD_OK) return rc;
+  const int n = c * c;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(dhd_cdiv(n, DHD_WAVE)), dim3(kEwBlock), 0, st, a.partial, gw, n, kPairWorkers);
+  DHD_LAUNCH_CHECK();
+  return DHD_OK;
+}
+
+// Layer 1 of the backward in one launch (sfa_gemm_pair1.h): du, this call's conv1 weight gradient and the du-part of dL/da per
+// (pair-worker, sample)
+int launch_pair1(const Pair1Args& a, float* gw, int c, hipStream_t st) {
+  const size_t shmem = pair1_lds_bytes(c);
+  int rc;
+  if (c == 256) rc = launch_lds<pw_pair1_kernel<256, 2, WgFirstStep>>(dim3(kPairGrid), dim3(512), shmem, shmem, st, a);
+  else if (c == 128) rc = launch_lds<pw_pair1_kernel<128, 2, WgFirstStep>>(dim3(kPairGrid), dim3(256), shmem, shmem, st, a);
   else return DHD_EUNSUPPORTED;
   if (rc != DHD_OK) return rc;
   const int n = c * c;
@@ -1998,7 +2022,8 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
   // The folded flow (header comment): per layer, the data gradient first, leaving its prologue's result over g, then the weight
   // gradient on that one tensor, which also makes the sums pair_sums / blend1_da made in passes of their own.  The worker rows
   // live where scratch is dead: du's region during phase 1, g2's during phase 2.  Bit 4 of the switch: layer 2 as one launch on
-  // pairs of CUs (launch_pair), under the same gate, its 128 worker rows in du's region too.
+  // pairs of CUs (launch_pair), under the same gate, its 128 worker rows in du's region too; bit 8: layer 1 likewise (launch_pair1),
+  // its 128 + b rows at the head of g2's region.
   // The gate is `sync == nullptr`, not the entry point: the phase entry points keep the unfolded flow only because they always pass
   // a `sync`; a caller that cut the folded flow into phases would find gy, not g, in g2 / g1 between them.
   int fold = 0;
@@ -2065,7 +2090,16 @@ int stage_backward(const Plan& p, const TS* x, const dhd_sfa_weights* w, const v
   if (hi <= 1) return DHD_OK;
   if (sync) coef_in(tail1, S.loc1, w->conv1_b);
   DHD_LAUNCH_CHECK();
-  if (fold & 2) {
+  if (fold & 8) {
+    if constexpr (std::is_same_v<TS, float>) {
+      // du = W1^T dy1, dW1 = dy1 . u^T and the du-part of dL/da per (pair-worker, sample); g1 stays as it is
+      rc = launch_pair1(Pair1Args{g1, y1, TF(T.tab_g1), reinterpret_cast<const u32x4*>(sv + S.wp1t), x, SF(S.tab_a), du, TF(T.wpart), rows2, hw, b},
+                        grads->conv1_w, c, st);
+      if (rc != DHD_OK) return rc;
+      hipLaunchKernelGGL(fc_backward_kernel, dim3(b), dim3(kEwBlock), (size_t)(c + r + kEwBlock) * sizeof(float), st, TF(T.da1), rows2,
+                         SF(S.a1), SF(S.h), w->fc1_w, w->fc2_w, TF(T.dpre2), TF(T.dh), TF(T.ds), c, r, kPairWorkers, (hw + 31) / 32);
+    }
+  } else if (fold & 2) {
     if constexpr (std::is_same_v<TS, float>) {
       // du = W1^T dy1; dy1 stays in g1
       rc = launch_gemm(p, GemmCall<TS>{kDgrad1, g1, y1, cs, c, TF(T.tab_g1), sv + S.wp1t, nullptr, nullptr, nullptr, du, nullptr, nullptr, CuBlend{}, 0, g1},
