@@ -2,8 +2,17 @@
 // parameters and statistics)
 // for the dense callers of the hot path (ResNet-50, FPN, UNets, BEV encoder: 11 % of a DHD-S training step on
 // MIOpen's kernels, which move these tensors at 0.7-3.6 TB/s).  Forward: plane sums -> per-channel finalize
-// (double) -> y = x * scale + shift.  Backward: plane sums of g and g * (x - mean) -> coefficients ->
-// gx = c0 * g + c1 * x + c2.  Every pass streams 16-byte vectors; eight passes over the tensor in total.
+// (double) -> y = (x - mean) * scale + beta.  Backward: plane sums of g and g * (x - mean) -> coefficients ->
+// gx = c0 * g + c1 * (x - mean) + c2.  Every pass streams 16-byte vectors; eight passes over the tensor in total.
+//
+// Stated domain.  The forward sums are one-pass float32 sums of (x - shift) and (x - shift)^2, var = s2 / cnt - m^2 in double:
+// exact enough while |mean - shift| is of the order of the channel's spread.  shift is the MEDIAN OF THREE elements of the channel
+// (first, middle and last of sample 0 in NCHW; first, middle and last row in channels_last), read by the sum kernels and the
+// finalize alike: one element that is not typical of its channel -- the empty corner cell of a BEV map in a channel that sits at
+// an offset, a single outlier -- cannot become the shift.  Two of the three being untypical in the same direction is outside
+// the domain (the error is then that of an unshifted one-pass variance, 2^-24 (mean - shift)^2 / var).  Both outputs apply their
+// coefficients to the centred x - mean, never to x: a constant channel comes out as exactly beta, and the error does not grow
+// with |mean| * rstd beyond the rounding of the float32 mean itself.
 #include "vec16.h"
 
 namespace {
@@ -13,6 +22,13 @@ constexpr int kBnBlock = 256;
 template <typename T> using Vec = dhd::Vec16<T, true>;
 // the value Vec<T>::store leaves in memory
 template <typename T> __device__ __forceinline__ float rnd(float f) { return dhd::round2<T>(dhd::f32x2{f, f}).x; }
+
+// the shift of the one-pass sums: immune to one untypical element (a NaN among the three yields one of the others)
+__device__ __forceinline__ float median3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
+template <typename T> __device__ __forceinline__ float plane_shift(const T* __restrict__ x, int ch, int hw) {
+  const T* p = x + (size_t)ch * hw;   // sample 0
+  return median3((float)p[0], (float)p[hw / 2], (float)p[hw - 1]);
+}
 
 __device__ __forceinline__ float block_sum(float v, float* sm) {
   v = group_sum(v, DHD_WAVE);
@@ -25,8 +41,8 @@ __device__ __forceinline__ float block_sum(float v, float* sm) {
   return t;
 }
 
-// grid (chunks, n*c).  BWD == false: s1 = sum (x - shift), s2 = sum (x - shift)^2 with shift = the channel's first
-// value (keeps the float32 sums small);  BWD == true: s1 = sum g, s2 = sum g * (x - mean).
+// grid (chunks, n*c).  BWD == false: s1 = sum (x - shift), s2 = sum (x - shift)^2 with shift = plane_shift (keeps the
+// float32 sums small);  BWD == true: s1 = sum g, s2 = sum g * (x - mean).
 // part: [(n_idx * chunks + chunk)][2][c]
 template <typename T, bool BWD>
 __global__ __launch_bounds__(kBnBlock) void bn_plane_sums(const T* __restrict__ x, const T* __restrict__ g, const float* __restrict__ mean,
@@ -34,7 +50,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_plane_sums(const T* __restrict__ 
   __shared__ float sm[kBnBlock / DHD_WAVE];
   constexpr int N = Vec<T>::N;
   const int plane = blockIdx.y, ni = plane / c, ch = plane % c;
-  const float shift = BWD ? mean[ch] : (float)x[(size_t)ch * hw];
+  const float shift = BWD ? mean[ch] : plane_shift(x, ch, hw);
   const int nvec = hw / N, per = (nvec + gridDim.x - 1) / gridDim.x;
   const int lo = blockIdx.x * per, hi = min(nvec, lo + per);
   const T* xp = x + (size_t)plane * hw;
@@ -76,7 +92,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_plane_sums(const T* __restrict__ 
   }
 }
 
-// per channel: batch mean / biased variance from the shifted sums (double), running statistics, y = x*scale + shift
+// per channel: batch mean / biased variance from the shifted sums (double), running statistics, coef = (scale, beta)
 template <typename T>
 __global__ __launch_bounds__(kBnBlock) void bn_forward_finalize(const float* __restrict__ part, int n_part, const T* __restrict__ x, int hw,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -90,7 +106,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_forward_finalize(const float* __r
     s1 += (double)part[((size_t)q * 2) * c + ch];
     s2 += (double)part[((size_t)q * 2 + 1) * c + ch];
   }
-  const double cnt = (double)n * (double)hw, shift = (double)(float)x[(size_t)ch * hw];
+  const double cnt = (double)n * (double)hw, shift = (double)plane_shift(x, ch, hw);
   const double m = s1 / cnt, var = fmax(s2 / cnt - m * m, 0.0), mean = shift + m;   // (inf - inf clamps to 0, as torch's kernels do: an Inf input turns the channel's finite entries into -inf)
   const double rstd = 1.0 / sqrt(var + (double)eps);
   save_mean[ch] = (float)mean;
@@ -99,10 +115,10 @@ __global__ __launch_bounds__(kBnBlock) void bn_forward_finalize(const float* __r
   if (running_var) running_var[ch] = (float)((1.0 - factor) * running_var[ch] + factor * var * (cnt > 1.0 ? cnt / (cnt - 1.0) : 1.0));
   const double ga = gamma ? (double)gamma[ch] : 1.0, be = beta ? (double)beta[ch] : 0.0;
   coef[ch] = (float)(ga * rstd);
-  coef[c + ch] = (float)(be - mean * ga * rstd);
+  coef[c + ch] = (float)be;
 }
 
-// dgamma, dbeta and the coefficients of gx = c0*g + c1*x + c2
+// dgamma, dbeta and the coefficients of gx = c0*g + c1*(x - mean) + c2
 __global__ __launch_bounds__(kBnBlock) void bn_backward_finalize(const float* __restrict__ part, int n_part, const float* __restrict__ gamma,
                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
@@ -114,22 +130,23 @@ __global__ __launch_bounds__(kBnBlock) void bn_backward_finalize(const float* __
     s1 += (double)part[((size_t)q * 2) * c + ch];
     s2 += (double)part[((size_t)q * 2 + 1) * c + ch];
   }
-  const double cnt = (double)n * (double)hw, rs = (double)rstd[ch], mu = (double)mean[ch], ga = gamma ? (double)gamma[ch] : 1.0;
+  const double cnt = (double)n * (double)hw, rs = (double)rstd[ch], ga = gamma ? (double)gamma[ch] : 1.0;
   if (dgamma) dgamma[ch] = (float)(rs * s2);
   if (dbeta) dbeta[ch] = (float)s1;
-  const double c0 = ga * rs, c1 = -ga * rs * rs * rs * s2 / cnt, c2 = -ga * rs * s1 / cnt - c1 * mu;
+  const double c0 = ga * rs, c1 = -ga * rs * rs * rs * s2 / cnt, c2 = -ga * rs * s1 / cnt;
   coef[ch] = (float)c0;
   coef[c + ch] = (float)c1;
   coef[2 * c + ch] = (float)c2;
 }
 
-// out = k0[c]*a + k1[c]*b + k2[c]   (forward: a = x, k1 = 0;  backward: a = g, b = x).  grid (chunks, n*c)
+// forward (TWO == false, a = x): out = (a - mean[c])*k0[c] + k1[c];  backward (a = g, b = x): out = k0[c]*a + k1[c]*(b - mean[c]) + k2[c].
+// grid (chunks, n*c)
 template <typename T, bool TWO>
 __global__ __launch_bounds__(kBnBlock) void bn_affine(const T* __restrict__ a, const T* __restrict__ b, const float* __restrict__ coef,
-                                                      T* __restrict__ out, int c, int hw) {
+                                                      const float* __restrict__ mean, T* __restrict__ out, int c, int hw) {
   constexpr int N = Vec<T>::N;
   const int plane = blockIdx.y, ch = plane % c;
-  const float k0 = coef[ch], k1 = coef[c + ch], k2 = TWO ? coef[2 * c + ch] : 0.f;
+  const float k0 = coef[ch], k1 = coef[c + ch], k2 = TWO ? coef[2 * c + ch] : 0.f, mu = mean[ch];
   const int nvec = hw / N, per = (nvec + gridDim.x - 1) / gridDim.x;
   const int lo = blockIdx.x * per, hi = min(nvec, lo + per);
   const T* ap = a + (size_t)plane * hw;
@@ -140,7 +157,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_affine(const T* __restrict__ a, c
     Vec<T>::load(ap + (size_t)i * N, va);
     if (TWO) Vec<T>::load(bp + (size_t)i * N, vb);
 #pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = TWO ? fmaf(k0, va[k], fmaf(k1, vb[k], k2)) : fmaf(k0, va[k], k1);
+    for (int k = 0; k < N; ++k) r[k] = TWO ? fmaf(k0, va[k], fmaf(k1, vb[k] - mu, k2)) : fmaf(va[k] - mu, k0, k1);
     Vec<T>::store(op + (size_t)i * N, r);
   }
 }
@@ -163,7 +180,7 @@ int bn_forward_t(const T* x, int n, int c, int hw, const float* gamma, const flo
   hipLaunchKernelGGL((bn_plane_sums<T, false>), grid, dim3(kBnBlock), 0, st, x, (const T*)nullptr, (const float*)nullptr, part, c, hw);
   hipLaunchKernelGGL((bn_forward_finalize<T>), dim3(dhd_cdiv(c, kBnBlock)), dim3(kBnBlock), 0, st, part, n * chunks, x, hw, gamma, beta, rm, rv,
                      factor, eps, save_mean, save_rstd, coef, n, c);
-  hipLaunchKernelGGL((bn_affine<T, false>), grid, dim3(kBnBlock), 0, st, x, (const T*)nullptr, coef, y, c, hw);
+  hipLaunchKernelGGL((bn_affine<T, false>), grid, dim3(kBnBlock), 0, st, x, (const T*)nullptr, coef, save_mean, y, c, hw);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -178,7 +195,7 @@ int bn_backward_t(const T* x, const T* gy, int n, int c, int hw, const float* ga
   hipLaunchKernelGGL((bn_plane_sums<T, true>), grid, dim3(kBnBlock), 0, st, x, gy, mean, part, c, hw);
   hipLaunchKernelGGL(bn_backward_finalize, dim3(dhd_cdiv(c, kBnBlock)), dim3(kBnBlock), 0, st, part, n * chunks, gamma, mean, rstd, dgamma,
                      dbeta, coef, n, c, hw);
-  hipLaunchKernelGGL((bn_affine<T, true>), grid, dim3(kBnBlock), 0, st, gy, x, coef, gx, c, hw);
+  hipLaunchKernelGGL((bn_affine<T, true>), grid, dim3(kBnBlock), 0, st, gy, x, coef, mean, gx, c, hw);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -188,8 +205,8 @@ int bn_backward_t(const T* x, const T* gy, int n, int c, int hw, const float* ga
 // walks down the rows (the kBnBlock threads of a workgroup cover vpb <= 16 vectors of R = 256 / vpb consecutive rows per step:
 // cl_grid); its N sums stay in registers and meet those of the other row lanes in LDS once per workgroup.
 // Optional fused epilogues of the dense callers' BatchNorm -> ReLU and BatchNorm -> (+ residual) -> ReLU pairs:
-//   forward   y = max(0, k0*x + k1 [+ res])
-//   backward  g' = g where the forward output was positive, else 0; the mask is recomputed from x and the saved (k0, k1)
+//   forward   y = max(0, (x - mean)*k0 + k1 [+ res])      (k0, k1) = (gamma * rstd, beta): save_affine
+//   backward  g' = g where the forward output was positive, else 0; the mask is recomputed from x, the saved mean and (k0, k1)
 //             (MASK 1: same expression, same rounding to T as the forward's store) or read from the saved output (MASK 2: the
 //             residual form, which also hands g' to the residual branch).
 // part: [2][c][n_part]
@@ -215,6 +232,18 @@ inline ClGrid cl_grid(long rows, int c, int vec) {
   return g;
 }
 
+// the shifts of the N channels from ch0 on: per channel the median of its elements in the first, the middle and the last row
+template <typename T>
+__device__ __forceinline__ void cl_shift(const T* __restrict__ x, int ch0, int c, long rows, float (&sh)[Vec<T>::N]) {
+  constexpr int N = Vec<T>::N;
+  float a[N], b[N], d[N];
+  Vec<T>::load(x + ch0, a);
+  Vec<T>::load(x + (size_t)(rows / 2) * c + ch0, b);
+  Vec<T>::load(x + (size_t)(rows - 1) * c + ch0, d);
+#pragma unroll
+  for (int k = 0; k < N; ++k) sh[k] = median3(a[k], b[k], d[k]);
+}
+
 template <typename T, bool BWD, int MASK>
 __global__ __launch_bounds__(kBnBlock) void bn_cl_sums(const T* __restrict__ x, const T* __restrict__ g, const T* __restrict__ y,
                                                        const float* __restrict__ mean, const float* __restrict__ fco,
@@ -231,9 +260,14 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_sums(const T* __restrict__ x, 
   if (r < R && v < V) {
     const int ch0 = v * N;
     float sh[N], f0[N], f1[N];
+    if (BWD) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) sh[k] = mean[ch0 + k];
+    } else {
+      cl_shift<T>(x, ch0, c, rows, sh);   // keeps the float32 sums small
+    }
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      sh[k] = BWD ? mean[ch0 + k] : (float)x[ch0 + k];   // forward: the channel's first value keeps the float32 sums small
       f0[k] = MASK == 1 ? fco[ch0 + k] : 0.f;
       f1[k] = MASK == 1 ? fco[c + ch0 + k] : 0.f;
     }
@@ -243,7 +277,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_sums(const T* __restrict__ x, 
         const float da = a[k] - sh[k];
         if (BWD) {
           float gg = ga[k];
-          if (MASK == 1) gg = rnd<T>(fmaf(f0[k], a[k], f1[k])) > 0.f ? gg : 0.f;
+          if (MASK == 1) gg = rnd<T>(fmaf(da, f0[k], f1[k])) > 0.f ? gg : 0.f;   // BWD: da = a - mean, the forward's expression
           if (MASK == 2) gg = ya[k] > 0.f ? gg : 0.f;
           s1[k] += gg;
           s2[k] = fmaf(gg, da, s2[k]);
@@ -331,7 +365,8 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_forward_finalize(const float* 
   double s1, s2;
   fold_parts(part, n_part, c, ch, lane, &s1, &s2);
   if (lane) return;
-  const double shift = (double)(float)x[ch];
+  const long rows = (long)cnt;
+  const double shift = (double)median3((float)x[ch], (float)x[(size_t)(rows / 2) * c + ch], (float)x[(size_t)(rows - 1) * c + ch]);
   const double m = s1 / cnt, var = fmax(s2 / cnt - m * m, 0.0), mean = shift + m;   // (inf - inf clamps to 0, as torch's kernels do: an Inf input turns the channel's finite entries into -inf)
   const double rstd = 1.0 / sqrt(var + (double)eps);
   save_mean[ch] = (float)mean;
@@ -340,7 +375,7 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_forward_finalize(const float* 
   if (running_var) running_var[ch] = (float)((1.0 - factor) * running_var[ch] + factor * var * (cnt > 1.0 ? cnt / (cnt - 1.0) : 1.0));
   const double ga = gamma ? (double)gamma[ch] : 1.0, be = beta ? (double)beta[ch] : 0.0;
   coef[ch] = (float)(ga * rstd);
-  coef[c + ch] = (float)(be - mean * ga * rstd);
+  coef[c + ch] = (float)be;
 }
 
 __global__ __launch_bounds__(kBnBlock) void bn_cl_backward_finalize(const float* __restrict__ part, int n_part, const float* __restrict__ gamma,
@@ -352,19 +387,20 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_backward_finalize(const float*
   double s1, s2;
   fold_parts(part, n_part, c, ch, lane, &s1, &s2);
   if (lane) return;
-  const double rs = (double)rstd[ch], mu = (double)mean[ch], ga = gamma ? (double)gamma[ch] : 1.0;
+  const double rs = (double)rstd[ch], ga = gamma ? (double)gamma[ch] : 1.0;
   if (dgamma) dgamma[ch] = (float)(rs * s2);
   if (dbeta) dbeta[ch] = (float)s1;
-  const double c0 = ga * rs, c1 = -ga * rs * rs * rs * s2 / cnt, c2 = -ga * rs * s1 / cnt - c1 * mu;
+  const double c0 = ga * rs, c1 = -ga * rs * rs * rs * s2 / cnt, c2 = -ga * rs * s1 / cnt;
   coef[ch] = (float)c0;
   coef[c + ch] = (float)c1;
   coef[2 * c + ch] = (float)c2;
 }
 
-// y = k0*x + k1, optionally + res, optionally max(0, .)
+// y = (x - mean)*k0 + k1, optionally + res, optionally max(0, .)
 template <typename T, bool RELU, bool ADD>
 __global__ __launch_bounds__(kBnBlock) void bn_cl_apply_fwd(const T* __restrict__ x, const T* __restrict__ res, const float* __restrict__ coef,
-                                                            T* __restrict__ y, int c, long rows, int rpb, int vpb) {
+                                                            const float* __restrict__ mean, T* __restrict__ y, int c, long rows, int rpb,
+                                                            int vpb) {
   constexpr int N = Vec<T>::N;
   const int V = c / N, R = kBnBlock / vpb;
   const int vl = threadIdx.x % vpb, r = threadIdx.x / vpb;
@@ -372,16 +408,16 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_apply_fwd(const T* __restrict_
   if (r >= R || v >= V) return;
   const long lo = (long)blockIdx.x * rpb, hi = min(rows, lo + (long)rpb);
   const int ch0 = v * N;
-  float k0[N], k1[N];
+  float k0[N], k1[N], mu[N];
 #pragma unroll
-  for (int k = 0; k < N; ++k) { k0[k] = coef[ch0 + k]; k1[k] = coef[c + ch0 + k]; }
+  for (int k = 0; k < N; ++k) { k0[k] = coef[ch0 + k]; k1[k] = coef[c + ch0 + k]; mu[k] = mean[ch0 + k]; }
   constexpr int U = ADD ? 2 : 4;
   long row = lo + r;
   auto one = [&](const float (&a)[N], const float (&b)[N], size_t o) {
     float out[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      float t = fmaf(k0[k], a[k], k1[k]);
+      float t = fmaf(a[k] - mu[k], k0[k], k1[k]);
       if (ADD) t += b[k];
       out[k] = RELU ? (t < 0.f ? 0.f : t) : t;   // not fmaxf: a NaN must come out as NaN, as torch.relu gives (fmaxf(NaN, 0) = 0)
     }
@@ -407,11 +443,12 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_apply_fwd(const T* __restrict_
   }
 }
 
-// gx = c0*g' + c1*x + c2 with g' the masked gradient (MASK as in bn_cl_sums); MASK 2 also stores g' for the residual branch
+// gx = c0*g' + c1*(x - mean) + c2 with g' the masked gradient (MASK as in bn_cl_sums); MASK 2 also stores g' for the residual branch
 template <typename T, int MASK>
 __global__ __launch_bounds__(kBnBlock) void bn_cl_apply_bwd(const T* __restrict__ x, const T* __restrict__ g, const T* __restrict__ y,
                                                             const float* __restrict__ coef, const float* __restrict__ fco,
-                                                            T* __restrict__ gx, T* __restrict__ gres, int c, long rows, int rpb, int vpb) {
+                                                            const float* __restrict__ mean, T* __restrict__ gx, T* __restrict__ gres, int c,
+                                                            long rows, int rpb, int vpb) {
   constexpr int N = Vec<T>::N;
   const int V = c / N, R = kBnBlock / vpb;
   const int vl = threadIdx.x % vpb, r = threadIdx.x / vpb;
@@ -419,10 +456,10 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_apply_bwd(const T* __restrict_
   if (r >= R || v >= V) return;
   const long lo = (long)blockIdx.x * rpb, hi = min(rows, lo + (long)rpb);
   const int ch0 = v * N;
-  float c0[N], c1[N], c2[N], f0[N], f1[N];
+  float c0[N], c1[N], c2[N], f0[N], f1[N], mu[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    c0[k] = coef[ch0 + k]; c1[k] = coef[c + ch0 + k]; c2[k] = coef[2 * c + ch0 + k];
+    c0[k] = coef[ch0 + k]; c1[k] = coef[c + ch0 + k]; c2[k] = coef[2 * c + ch0 + k]; mu[k] = mean[ch0 + k];
     f0[k] = MASK == 1 ? fco[ch0 + k] : 0.f;
     f1[k] = MASK == 1 ? fco[c + ch0 + k] : 0.f;
   }
@@ -433,10 +470,11 @@ __global__ __launch_bounds__(kBnBlock) void bn_cl_apply_bwd(const T* __restrict_
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       float gg = ga[k];
-      if (MASK == 1) gg = rnd<T>(fmaf(f0[k], a[k], f1[k])) > 0.f ? gg : 0.f;
+      const float da = a[k] - mu[k];
+      if (MASK == 1) gg = rnd<T>(fmaf(da, f0[k], f1[k])) > 0.f ? gg : 0.f;
       if (MASK == 2) gg = ya[k] > 0.f ? gg : 0.f;
       gm[k] = gg;
-      out[k] = fmaf(c0[k], gg, fmaf(c1[k], a[k], c2[k]));
+      out[k] = fmaf(c0[k], gg, fmaf(c1[k], da, c2[k]));
     }
     Vec<T>::store(gx + ch0 + o, out);
     if (MASK == 2 && gres) Vec<T>::store(gres + ch0 + o, gm);
@@ -479,9 +517,9 @@ int bn_cl_forward_t(const T* x, const T* res, long rows, int c, int flags, const
   hipLaunchKernelGGL((bn_cl_forward_finalize<T>), dim3(dhd_cdiv(c, kBnBlock / DHD_WAVE)), blk, 0, st, ws, g.n_part, x, gamma, beta, rm, rv,
                      factor, eps, save_mean, save_rstd, save_affine, (double)rows, c);
   const bool relu = flags & (DHD_BN_RELU | DHD_BN_ADD), add = flags & DHD_BN_ADD;
-  if (add) hipLaunchKernelGGL((bn_cl_apply_fwd<T, true, true>), grid, blk, 0, st, x, res, save_affine, y, c, rows, g.rpb, g.vpb);
-  else if (relu) hipLaunchKernelGGL((bn_cl_apply_fwd<T, true, false>), grid, blk, 0, st, x, res, save_affine, y, c, rows, g.rpb, g.vpb);
-  else hipLaunchKernelGGL((bn_cl_apply_fwd<T, false, false>), grid, blk, 0, st, x, res, save_affine, y, c, rows, g.rpb, g.vpb);
+  if (add) hipLaunchKernelGGL((bn_cl_apply_fwd<T, true, true>), grid, blk, 0, st, x, res, save_affine, save_mean, y, c, rows, g.rpb, g.vpb);
+  else if (relu) hipLaunchKernelGGL((bn_cl_apply_fwd<T, true, false>), grid, blk, 0, st, x, res, save_affine, save_mean, y, c, rows, g.rpb, g.vpb);
+  else hipLaunchKernelGGL((bn_cl_apply_fwd<T, false, false>), grid, blk, 0, st, x, res, save_affine, save_mean, y, c, rows, g.rpb, g.vpb);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
@@ -498,9 +536,9 @@ int bn_cl_backward_t(const T* x, const T* y, const T* gy, long rows, int c, int 
   else hipLaunchKernelGGL((bn_cl_sums<T, true, 0>), grid, blk, 0, st, x, gy, y, mean, save_affine, ws, c, rows, g.rpb, g.n_part, g.vpb);
   hipLaunchKernelGGL(bn_cl_backward_finalize, dim3(dhd_cdiv(c, kBnBlock / DHD_WAVE)), blk, 0, st, ws, g.n_part, gamma, mean, rstd, dgamma, dbeta,
                      coef, (double)rows, c);
-  if (mask == 2) hipLaunchKernelGGL((bn_cl_apply_bwd<T, 2>), grid, blk, 0, st, x, gy, y, coef, save_affine, gx, gres, c, rows, g.rpb, g.vpb);
-  else if (mask == 1) hipLaunchKernelGGL((bn_cl_apply_bwd<T, 1>), grid, blk, 0, st, x, gy, y, coef, save_affine, gx, gres, c, rows, g.rpb, g.vpb);
-  else hipLaunchKernelGGL((bn_cl_apply_bwd<T, 0>), grid, blk, 0, st, x, gy, y, coef, save_affine, gx, gres, c, rows, g.rpb, g.vpb);
+  if (mask == 2) hipLaunchKernelGGL((bn_cl_apply_bwd<T, 2>), grid, blk, 0, st, x, gy, y, coef, save_affine, mean, gx, gres, c, rows, g.rpb, g.vpb);
+  else if (mask == 1) hipLaunchKernelGGL((bn_cl_apply_bwd<T, 1>), grid, blk, 0, st, x, gy, y, coef, save_affine, mean, gx, gres, c, rows, g.rpb, g.vpb);
+  else hipLaunchKernelGGL((bn_cl_apply_bwd<T, 0>), grid, blk, 0, st, x, gy, y, coef, save_affine, mean, gx, gres, c, rows, g.rpb, g.vpb);
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }

@@ -214,7 +214,9 @@ __global__ __launch_bounds__(kBlock) void swin_ffn_kernel(const X* __restrict__ 
     float tot = sum8(s);
     tot += __shfl_xor(tot, 32, DHD_WAVE);
     mean = tot * (1.f / C);
-    float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // the centred pass also sums the residuals and corrects the mean by their average: the rounding of the float32 sum, some
+    // 2^-24 |mean|, is otherwise multiplied by rstd (316 on a constant row, whose exact xn is beta)
+    float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, e[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       float v[8];
@@ -222,12 +224,16 @@ __global__ __launch_bounds__(kBlock) void swin_ffn_kernel(const X* __restrict__ 
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float d = v[j] - mean;
+        e[j] += d;
         q[j] = fmaf(d, d, q[j]);
       }
     }
-    float var = sum8(q);
+    float var = sum8(q), de = sum8(e);
     var += __shfl_xor(var, 32, DHD_WAVE);
-    rstd = 1.f / sqrtf(var * (1.f / C) + eps);
+    de += __shfl_xor(de, 32, DHD_WAVE);
+    de *= 1.f / C;
+    mean += de;
+    rstd = 1.f / sqrtf(fmaxf(var * (1.f / C) - de * de, 0.f) + eps);
   }
 
   // the B fragments of GEMM-1: xf[ks][part] = normalised elements 16 ks + 8 h + j of the row

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void swin_ffn_bwd_kernel(const X* __restric
       float tot = sum8(s);
       tot += __shfl_xor(tot, 32, DHD_WAVE);
       mean = tot * (1.f / C);
-      float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, e[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         float v[8];
@@ -227,12 +227,16 @@ __global__ __launch_bounds__(kBlock) void swin_ffn_bwd_kernel(const X* __restric
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float d = v[j] - mean;
+          e[j] += d;
           q[j] = fmaf(d, d, q[j]);
         }
       }
-      float var = sum8(q);
+      float var = sum8(q), de = sum8(e);
       var += __shfl_xor(var, 32, DHD_WAVE);
-      rstd = 1.f / sqrtf(var * (1.f / C) + eps);
+      de += __shfl_xor(de, 32, DHD_WAVE);
+      de *= 1.f / C;
+      mean += de;   // the forward's correction of the mean by the residuals' average
+      rstd = 1.f / sqrtf(fmaxf(var * (1.f / C) - de * de, 0.f) + eps);
     }
     // xn, rounded once to M: the B fragments of the h GEMM, and the operand of dW1
     // (`off` is 0: inside the tile loop a value the compiler cannot see through, or the loads would be hoisted out of the loop

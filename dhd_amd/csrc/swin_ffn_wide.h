@@ -182,19 +182,22 @@ __global__ __launch_bounds__(kWideBlock) void swin_ffn_wide_kernel(const X* __re
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < NV; ++k) s += sum8(v[k]);
-        const float mean = wave_sum(s) * (1.f / C);
-        float q = 0.f;
+        float mean = wave_sum(s) * (1.f / C);
+        // the centred pass also sums the residuals and corrects the mean by their average (swin_ffn.hip says why)
+        float q = 0.f, e = 0.f;
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
           float d[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            d[j] = v[k][j] - mean;
-            d[j] *= d[j];
-          }
+          for (int j = 0; j < 8; ++j) d[j] = v[k][j] - mean;
+          e += sum8(d);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) d[j] *= d[j];
           q += sum8(d);
         }
-        const float rstd = 1.f / sqrtf(wave_sum(q) * (1.f / C) + eps);
+        const float de = wave_sum(e) * (1.f / C);
+        mean += de;
+        const float rstd = 1.f / sqrtf(fmaxf(wave_sum(q) * (1.f / C) - de * de, 0.f) + eps);
 #pragma unroll
         for (int k = 0; k < NV; ++k)
 #pragma unroll

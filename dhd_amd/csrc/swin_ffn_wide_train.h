@@ -155,13 +155,14 @@ __global__ __launch_bounds__(kWideBlock) void swin_ffn_wide_bwd_kernel(const X* 
       load_raw<X>(x + (size_t)p * C + 8 * lane, 0, raw);   // channels 8 lane + j
       widen8<X>(raw, v);
       // the wide forward's statistics, operation for operation
-      const float mean = wave_sum(sum8(v)) * (1.f / C);
+      float mean = wave_sum(sum8(v)) * (1.f / C);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        d[j] = v[j] - mean;
-        d[j] *= d[j];
-      }
-      const float rstd = 1.f / sqrtf(wave_sum(sum8(d)) * (1.f / C) + eps);
+      for (int j = 0; j < 8; ++j) d[j] = v[j] - mean;
+      const float de = wave_sum(sum8(d)) * (1.f / C);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d[j] *= d[j];
+      mean += de;   // the forward's correction of the mean by the residuals' average
+      const float rstd = 1.f / sqrtf(fmaxf(wave_sum(sum8(d)) * (1.f / C) - de * de, 0.f) + eps);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = ((v[j] - mean) * rstd) * gv[j] + bv[j];
       u32x4 parts[P];

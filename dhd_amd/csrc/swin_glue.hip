@@ -62,7 +62,11 @@ __device__ __forceinline__ void load_row(const T* p, bool on, int lane, int lane
   }
 }
 
-// mean and 1 / sqrt(var + eps) of the row held by the group: the sum, then the centred sum of squares
+// mean and 1 / sqrt(var + eps) of the row held by the group: the sum, then the centred sum of squares.  The centred pass also
+// sums the residuals d = x - mean and corrects the mean by their average: the float32 sum leaves the mean off by some
+// 2^-24 |mean|, which (x - mean) rstd multiplies by up to eps^-1/2 = 316 -- on a constant row at 100, whose exact result is beta,
+// that was 3e-3.  With the correction a constant row gives d = 0 and beta exactly; var = sum d^2 / c - (sum d / c)^2 is the
+// variance about the corrected mean.
 template <int STEPS>
 __device__ __forceinline__ void row_stats(const float (&v)[STEPS][8], int lane, int lanes, int nvec, int c, float eps, float& mean, float& rstd) {
   float s = 0.f;
@@ -71,18 +75,21 @@ __device__ __forceinline__ void row_stats(const float (&v)[STEPS][8], int lane, 
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += v[i][k];
   mean = group_sum(s, lanes) / (float)c;
-  float q = 0.f;
+  float q = 0.f, e = 0.f;
 #pragma unroll
   for (int i = 0; i < STEPS; ++i) {
     if (i * lanes + lane < nvec) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float d = v[i][k] - mean;
+        e += d;
         q += d * d;
       }
     }
   }
-  rstd = 1.f / sqrtf(group_sum(q, lanes) / (float)c + eps);
+  const float de = group_sum(e, lanes) / (float)c;
+  mean += de;
+  rstd = 1.f / sqrtf(fmaxf(group_sum(q, lanes) / (float)c - de * de, 0.f) + eps);
 }
 
 // every pass of the loop is made by all lanes of the block (the bound depends on blockIdx alone), so the shuffles of row_stats

@@ -97,7 +97,9 @@ __device__ __forceinline__ void merge_load(const TX* x, const MergeGeom& g, long
   }
 }
 
-// mean and 1 / sqrt(var + eps) over the n values of the row the group holds: the sum, then the centred sum of squares
+// mean and 1 / sqrt(var + eps) over the n values of the row the group holds: the sum, then the centred sum of squares; the
+// centred pass also sums the residuals and corrects the mean by their average (swin_glue.hip's row_stats says why: a constant row
+// then gives exactly beta)
 template <int STEPS, int N>
 __device__ __forceinline__ void row_stats(const float (&v)[STEPS][N], int lane, int lanes, int units, int n, float eps, float& mean, float& rstd) {
   float s = 0.f;
@@ -106,18 +108,21 @@ __device__ __forceinline__ void row_stats(const float (&v)[STEPS][N], int lane, 
 #pragma unroll
     for (int k = 0; k < N; ++k) s += v[i][k];
   mean = group_sum(s, lanes) / (float)n;
-  float q = 0.f;
+  float q = 0.f, e = 0.f;
 #pragma unroll
   for (int i = 0; i < STEPS; ++i) {
     if (i * lanes + lane < units) {
 #pragma unroll
       for (int k = 0; k < N; ++k) {
         const float d = v[i][k] - mean;
+        e += d;
         q += d * d;
       }
     }
   }
-  rstd = 1.f / sqrtf(group_sum(q, lanes) / (float)n + eps);
+  const float de = group_sum(e, lanes) / (float)n;
+  mean += de;
+  rstd = 1.f / sqrtf(fmaxf(group_sum(q, lanes) / (float)n - de * de, 0.f) + eps);
 }
 
 // every pass of the loop is made by all lanes of the block (the bound depends on blockIdx alone), so the shuffles of row_stats

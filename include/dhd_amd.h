@@ -670,8 +670,8 @@ int dhd_bn_train_backward(const void* x, const void* grad_y, int dtype, int n, i
  *     what torch.channels_last tensors are in memory -- with c a multiple of 4 (float32) or 8 elements.  `flags` fuses the
  *     element-wise operators that follow the normalisation in the dense callers (resnet.py's Bottleneck, mmcv's ConvModule):
  *       DHD_BN_RELU  y = max(0, bn(x));   DHD_BN_ADD  y = max(0, bn(x) + residual)   (ADD implies the ReLU).
- *     Backward takes the gradient with respect to that y: its ReLU mask is recomputed from x and save_affine (= the forward's
- *     per-channel scale | shift, [2*c]; RELU) or read from the saved output y (ADD), and with ADD grad_residual (may be NULL)
+ *     Backward takes the gradient with respect to that y: its ReLU mask is recomputed from x, save_mean and save_affine (= the
+ *     forward's per-channel gamma*rstd | beta, [2*c], of y = (x - mean)*scale + beta; RELU) or read from the saved output y (ADD), and with ADD grad_residual (may be NULL)
  *     receives the masked gradient.  Without flags y / residual / grad_residual may be NULL in backward.
  *     Workspace: dhd_bn_nhwc_workspace_bytes. */
 #define DHD_BN_RELU 1
