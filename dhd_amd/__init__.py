@@ -27,6 +27,7 @@ from . import swin_ffn  # noqa: F401  (the module, callable as its function swin
 from .swin_ffn import swin_ffn_infer, swin_ffn_supported, swin_ffn_train_supported, swin_ffn_train_wide_supported  # noqa: F401
 from .swin_seam import patch_merge_norm, patch_embed_norm, swin_seam_supported  # noqa: F401
 from .unet_seam import max_pool2x2, conv_transpose2x2_cat, unet_seam_supported, unet_seam_routed  # noqa: F401
+from .stereo_cv import stereo_sampling_grid, stereo_cost_volume, stereo_cv_supported, stereo_cv_routed  # noqa: F401
 from .ray_metrics import RayIoU, calc_rayiou, generate_lidar_rays, render_forward  # noqa: F401
 
 __version__ = '0.1.0'
@@ -191,4 +192,20 @@ def fused_unet_seams(model, on=True):
     switched = [m for m in model.modules() if isinstance(m, (_Down, _Up))]
     for m in switched:
         m.fused_seam = bool(on)
+    return switched
+
+
+def fused_stereo_cost_volume(model, on=True):
+    """Sets `fused_cost_volume` on every HeightNet / DepthNet of `model` and returns the modules it switched.  With it
+    `calculate_cost_volumn` (the temporal DepthNet of DHD-M and DHD-L) runs as `stereo_cost_volume`: the sampling positions of
+    `gen_grid` are evaluated inside the kernel from the camera matrices, and the stereo features are read in their own dtype
+    (float32, float16, bfloat16), in place where their memory is NHWC -- wherever the call is supported (stereo_cv_supported) and
+    the measurement routed that channel class and dtype to it (stereo_cv.ROUTED).  A feature shape the operator does not take, with
+    a separable frustum, gets its grid from `stereo_sampling_grid` and keeps today's kernel; every other call keeps today's path bit
+    for bit.  float32 results are today's bytes; half results are within 1e-4 + 2 eps |ref| of today's.  It is a switch of its
+    own: it sets none of the other switches."""
+    from .depthnet import _LiftNetBase
+    switched = [m for m in model.modules() if isinstance(m, _LiftNetBase)]
+    for m in switched:
+        m.fused_cost_volume = bool(on)
     return switched

@@ -612,3 +612,5 @@ extern "C" int dhd_stereo_cost_volume(const float* prev_nhwc, const float* curr_
   DHD_LAUNCH_CHECK();
   return DHD_OK;
 }
+
+#include "stereo_cv.h"

@@ -381,10 +381,17 @@ class _LiftNetBase(nn.Module):
         hi, wi = hf * 4, wf * 4
         B, N, _ = metas['post_trans'].shape
         D, H, W, _ = metas['frustum'].shape
+        hip = self.use_hip_cost_volume and curr.is_cuda and c % group == 0 and c <= 1024 and D <= 256
+        if self.fused_cost_volume and hip:
+            from . import stereo_cv   # positions from the camera matrices inside the kernel, features read in their own type
+            cv = stereo_cv.module_cost_volume(self, metas, prev.view(B * N, -1, H, W), curr.view(B * N, -1, H, W), D, hi, wi,
+                                              (c // group - 1) * group)
+            if cv is not None:
+                return cv
         grid = self.gen_grid(metas, B, N, D, H, W, hi, wi).to(curr.dtype)
         prev = prev.view(B * N, -1, H, W)
         curr = curr.view(B * N, -1, H, W)
-        if self.use_hip_cost_volume and curr.is_cuda and c % group == 0 and c <= 1024 and D <= 256:
+        if hip:
             return self._hip_cost_volume(prev, curr, grid, D, (c // group - 1) * group)
         cost = 0
         warped = None
@@ -398,6 +405,8 @@ class _LiftNetBase(nn.Module):
         return (-cost).softmax(dim=1)
 
     use_hip_cost_volume = True
+    # opt-in (dhd_amd.fused_stereo_cost_volume / DHD_STEREO_CV=1): dhd_amd.stereo_cv where the call is supported and routed
+    fused_cost_volume = bool(os.environ.get('DHD_STEREO_CV'))
 
     def _hip_cost_volume(self, prev, curr, grid, n_depth, flag_channel):
         """The same cost volume in one HIP kernel (csrc/deform.hip: stereo_cost_volume_kernel); float32."""
